@@ -36,7 +36,7 @@ def test_world_size_must_match_gpus():
 def test_two_ranks_debug_one_gpu_end_to_end():
     """Self-spawned 2-rank run on the box's single GPU (debug transport): the N>1 path of bench.py -
     snapshot file shared between ranks, sharded batch, library-side all-gather - runs end to end."""
-    r = _run(["--gpus", "2", "--n-docs", "20000", "--batch", "64", "--steps", "3", "--warmup", "1",
+    r = _run(["--gpus", "2", "--full", "--n-docs", "20000", "--batch", "64", "--steps", "3", "--warmup", "1",
               "--no-cpu-baseline", "--no-single-latency"], env={"PS_BENCH_DEBUG_ONE_GPU": "1"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

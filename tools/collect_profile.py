@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""gpurun_out/prof_<cfg>/ (tools/profile_bench.sh) -> profiles/r<round>_<cfg>_rocprof_summary.txt (kernel
+"""$PS_PROFILE_OUT/prof_<cfg>/ (tools/profile_bench.sh; default profile_out/) -> profiles/r<round>_<cfg>_rocprof_summary.txt (kernel
 trace + every PMC pass, one text file) and profiles/roofline_<cfg>.json (the derivation bench.py reads).
 usage: collect_profile.py <round tag, e.g. r02> <cfg> [<cfg> ...]"""
 import os
@@ -9,7 +9,7 @@ import sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1]
 for cfg in sys.argv[2:]:
-    d = os.path.join(root, "gpurun_out", "prof_" + cfg)
+    d = os.path.join(os.environ.get("PS_PROFILE_OUT") or os.path.join(root, "profile_out"), "prof_" + cfg)
     out = os.path.join(root, "profiles", "%s_%s_rocprof_summary.txt" % (tag, cfg))
     with open(out, "w") as f:
         f.write("# %s %s: rocprofv3 passes of bench.py on one MI355X, summarised by tools/rocpd_summary.py; one pass per "

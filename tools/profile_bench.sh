@@ -1,18 +1,18 @@
 #!/bin/bash
-# Runs on the GPU box (via gpurun): rocprofv3 kernel trace + PMC passes of bench.py (each pass its own
+# Runs on an MI355X: rocprofv3 kernel trace + PMC passes of bench.py --full (each pass its own
 # run and its own timeout; counters never share a run with a trace domain), text summaries into
-# gpurun_out/prof_<tag>/, then tools/derive_roofline.py turns them into the derivation JSON that
+# $PS_PROFILE_OUT/prof_<tag>/ (default: profile_out/ in the repository, ignored by git), then tools/derive_roofline.py turns them into the derivation JSON that
 # bench.py prices its roofline against (copy both into profiles/ to have them judged).
 #   usage: tools/profile_bench.sh <tag> <git head> [bench args...]
 set -u
 TAG=$1; shift
 HEAD=$1; shift
 R=${GRAFT_REPO_ROOT:-$PWD}
-OUT=$R/gpurun_out/prof_$TAG
+OUT=${PS_PROFILE_OUT:-$R/profile_out}/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 cd $R
-BENCH="python bench.py --no-cpu-baseline --no-single-latency --no-bulk-index --no-streaming-leg --no-alternating-boosts-leg --no-update-leg $*"
+BENCH="python bench.py --full --no-cpu-baseline --no-single-latency --no-bulk-index --no-streaming-leg --no-alternating-boosts-leg --no-update-leg $*"
 echo "rocprofv3 <pass> -- $BENCH --steps 6 --warmup 2" > $OUT/command.txt
 run() {  # name, rocprof args...
   local name=$1; shift
