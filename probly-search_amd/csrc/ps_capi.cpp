@@ -654,7 +654,7 @@ ps_status ps_snapshot_query_batch_device_planned_flat(ps_snapshot* snap, const p
     ps_batch_stats stats;
     if (!snap->engine->run_device_planned(*scorer, fields_boost, text, offsets, n_queries, top_k, d_keys, d_scores, d_counts,
                                           hip_stream, stats)) {
-      // (a zero_to_one batch K1dz does not take whole: straight to the host planner - run_device_flat would ask the device
+      // (a zero_to_one batch K1dz does not take whole, or a deep top-k batch: straight to the host planner - run_device_flat would ask the device
       // planner a second time: another count pass and another host wait before the same answer)
       std::vector<std::string_view> qs(n_queries);
       for (size_t i = 0; i < n_queries; ++i) qs[i] = std::string_view(text + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));

@@ -2733,6 +2733,112 @@ Plan sub_plan(const Plan& plan, size_t b, size_t e) {
   return p2;
 }
 
+// Deep top-k (PS_MAX_DEVICE_TOPK < top_k <= PS_MAX_DEEP_TOPK): stage 1 is full-result mode's - every query's run of
+// (doc, score) behind full_off / full_cnt -, then K4s k_deep_select (ps_kernels_select.hpp) picks the first top_k of
+// every run into the caller's block.  All device work is ordered on `st` and no result or count comes back to the
+// host.  A batch whose runs exceed the result budget is scored in consecutive slices of queries, each writing its own
+// rows; a single query is always one slice, however long its run (the budget bounds slices, not one query's run, and
+// a run longer than the LDS candidate buffer brings the same size of scratch again).  Enqueueing is not free of waits
+// with many slices: every slice stages its sub-plan in a pinned slot and takes a timer from the ring, and once
+// either ring wraps (N_STAGE slots, N_KTIMER timers) the host waits for the event of the slice that last used the entry.
+void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t top_k, void* d_keys,
+                  void* d_scores, void* d_counts, hipStream_t st) {
+  const Snapshot& s = *m.snap;
+  const size_t B = plan.qbeg.size() - 1;
+  refresh_tuning(m);
+  drop_ahead(m);
+  m.last_bounds_recomputed = false;
+  m.last_kt = nullptr;
+  if (!B) return;
+  // upper bound of matches per query: min(N, sum of its list lengths) - k_deep_offsets lays the runs out by the same rule
+  std::vector<uint64_t> cap(B + 1, 0);
+  for (size_t q = 0; q < B; ++q) {
+    uint64_t sum = 0;
+    for (uint32_t e = plan.qbeg[q]; e < plan.qbeg[q + 1]; ++e) sum += plan.entries[e].len;
+    cap[q + 1] = cap[q] + std::min<uint64_t>(sum, s.n_ids);
+  }
+  const uint64_t budget = (uint64_t)m.tune.full_budget_mb << 20;
+  std::vector<size_t> cut{0};  // slice i = queries [cut[i], cut[i + 1])
+  uint64_t max_cap = 0, max_run = 0;
+  size_t max_q = 0;
+  for (size_t qa = 0; qa < B;) {
+    size_t qb = qa + 1;
+    while (qb < B && (cap[qb + 1] - cap[qa]) * 12 <= budget && cap[qb + 1] - cap[qa] < 0xFFFFFFF0ull) ++qb;
+    max_cap = std::max(max_cap, cap[qb] - cap[qa]);
+    max_q = std::max(max_q, qb - qa);
+    cut.push_back(qb);
+    qa = qb;
+  }
+  for (size_t q = 0; q < B; ++q) max_run = std::max(max_run, cap[q + 1] - cap[q]);
+  if (m.tail_pending && m.tail_stream != st) PS_HIP(hipStreamWaitEvent(st, m.ev[0], 0));
+  m.tail_pending = false;
+  m.d_full_doc.ensure(max_cap + 1);
+  m.d_full_score.ensure(max_cap + 1);
+  m.d_full_off.ensure(max_q + 1);
+  m.d_full_cnt.ensure(max_q + 1);
+  const bool spills = max_run > (uint64_t)DEEP_CAND;  // only a run longer than the LDS candidate buffer can need the scratch
+  if (spills) {
+    m.d_sort_doc.ensure(max_cap + 1);
+    m.d_sort_score.ensure(max_cap + 1);
+  }
+  allow_lds(reinterpret_cast<const void*>(&k_deep_select), DEEP_LDS);
+  for (size_t i = 0; i + 1 < cut.size(); ++i) {
+    const size_t qa = cut[i], qb = cut[i + 1], nq = qb - qa;
+    const bool whole = nq == B;
+    const Plan part = whole ? Plan() : sub_plan(plan, qa, qb);
+    const Plan& pl = whole ? plan : part;
+    KParams kp;
+    EngineImpl::KTimer* kt = nullptr;
+    try {
+      stage_plan(m, sc, boosts, pl, st, kp, false, false);
+      kp.K = 1;
+      kp.full_doc = m.d_full_doc.p;
+      kp.full_score = m.d_full_score.p;
+      kp.full_off = m.d_full_off.p;
+      kp.full_cnt = m.d_full_cnt.p;
+      hipLaunchKernelGGL(k_deep_offsets, dim3(1), dim3(DEEP_NT), 0, st, kp.plan, kp.qbeg, (uint32_t)nq, kp.n_docs, m.d_full_off.p,
+                         m.d_full_cnt.p);
+      PS_HIP(hipGetLastError());
+      m.rebase_timers_if_stale(m.stream);
+      kt = &m.kt[m.next_kt];
+      m.next_kt = (m.next_kt + 1) % N_KTIMER;
+      m.harvest(*kt, true);
+      kt->split = false;
+      PS_HIP(hipEventRecord(kt->a, st));
+      launch_score<true>(m, sc, pl, kp, m.n_cu, st, kt->m);
+    } catch (...) {
+      forget_rows(m);
+      throw;
+    }
+    PS_HIP(hipEventRecord(kt->b, st));
+    kt->pending = true;
+    m.last_kt = kt;
+    DeepParams dp{};
+    dp.run_doc = m.d_full_doc.p;
+    dp.run_score = reinterpret_cast<uint64_t*>(m.d_full_score.p);
+    dp.tmp_doc = spills ? m.d_sort_doc.p : nullptr;
+    dp.tmp_score = spills ? m.d_sort_score.p : nullptr;
+    dp.off = m.d_full_off.p;
+    dp.cnt = m.d_full_cnt.p;
+    dp.keys = m.d_keys;
+    dp.out_keys = static_cast<uint64_t*>(d_keys);
+    dp.out_scores = static_cast<double*>(d_scores);
+    dp.out_counts = static_cast<uint32_t*>(d_counts);
+    dp.K = (uint32_t)top_k;
+    dp.row0 = (uint32_t)qa;
+    hipLaunchKernelGGL(k_deep_select, dim3((uint32_t)nq), dim3(DEEP_NT), DEEP_LDS, st, dp);
+    PS_HIP(hipGetLastError());
+    if (m.cur_zero_copy) {  // stage 1 reads the staging slot in place: fence it
+      PS_HIP(hipEventRecord(m.cur_stage->done, st));
+      m.cur_stage->pending = true;
+    }
+  }
+  m.wc_results += (uint64_t)B * top_k;
+  PS_HIP(hipEventRecord(m.ev[0], st));
+  m.tail_stream = st;
+  m.tail_pending = true;
+}
+
 }  // namespace
 
 namespace {
@@ -3018,7 +3124,8 @@ bool Engine::run_device_planned(const ps_scorer_desc& sc, const double* boosts, 
   const bool z = sc.kind == PS_SCORER_ZERO_TO_ONE;
   if (sc.kind != PS_SCORER_BM25 && !z) throw std::invalid_argument("the device planner handles the built-in scorers");
   if (s.F > (uint32_t)MAX_F) throw std::length_error("the GPU path supports at most 8 fields");
-  if (top_k < 1 || top_k > PS_MAX_DEVICE_TOPK) throw std::invalid_argument("top_k must be in [1, 64] for the device top-k path");
+  if (top_k < 1 || top_k > PS_MAX_DEEP_TOPK) throw std::invalid_argument("top_k must be in [1, 1024] for the device top-k path");
+  if (top_k > PS_MAX_DEVICE_TOPK) return false;  // the deep top-k path is planned on the host (run_device)
   std::lock_guard<std::mutex> lock(m.mu);
   PS_HIP(hipSetDevice(m.device));
   refresh_tuning(m);
@@ -3161,13 +3268,14 @@ void Engine::run_device(const ps_scorer_desc& sc, const double* boosts, const Pl
   EngineImpl& m = *impl_;
   const Snapshot& s = *m.snap;
   validate(s, sc, plan);
-  if (top_k < 1 || top_k > PS_MAX_DEVICE_TOPK)
-    throw std::invalid_argument("top_k must be in [1, 64] for the device top-k path");
+  if (top_k < 1 || top_k > PS_MAX_DEEP_TOPK)
+    throw std::invalid_argument("top_k must be in [1, 1024] for the device top-k path");
   std::lock_guard<std::mutex> lock(m.mu);
   PS_HIP(hipSetDevice(m.device));
   const double t0 = now_ms();
   hipStream_t st = stream ? (hipStream_t)stream : m.stream;
-  enqueue_topk(m, sc, boosts, plan, top_k, d_keys, d_scores, d_counts, st, false);
+  if (top_k > PS_MAX_DEVICE_TOPK) enqueue_deep(m, sc, boosts, plan, top_k, d_keys, d_scores, d_counts, st);
+  else enqueue_topk(m, sc, boosts, plan, top_k, d_keys, d_scores, d_counts, st, false);
   memset(&stats, 0, sizeof(stats));
   fill_stats(m, stats, s, plan, (uint64_t)(plan.qbeg.size() - 1) * top_k);
   if (!stream) {
@@ -3188,7 +3296,8 @@ void Engine::run_host(const ps_scorer_desc& sc, const double* boosts, const Plan
   memset(&stats, 0, sizeof(stats));
   const double t0 = now_ms();
 
-  if (top_k >= 1 && top_k <= PS_MAX_DEVICE_TOPK) {
+  if (top_k >= 1 && top_k <= PS_MAX_DEEP_TOPK) {
+    const bool deep = top_k > PS_MAX_DEVICE_TOPK;  // k_deep_select instead of the scoring kernels' own top-k: the same block
     std::lock_guard<std::mutex> lock(m.mu);
     PS_HIP(hipSetDevice(m.device));
     hipStream_t st = m.stream;
@@ -3206,7 +3315,8 @@ void Engine::run_host(const ps_scorer_desc& sc, const double* boosts, const Plan
       dres = reinterpret_cast<unsigned char*>(m.d_out_keys.p);
     }
     try {
-      enqueue_topk(m, sc, boosts, plan, top_k, dres, dres + nb * 8, dres + nb * 16, st, true);
+      if (deep) enqueue_deep(m, sc, boosts, plan, top_k, dres, dres + nb * 8, dres + nb * 16, st);
+      else enqueue_topk(m, sc, boosts, plan, top_k, dres, dres + nb * 8, dres + nb * 16, st, true);
       if (!direct && res_bytes) PS_HIP(hipMemcpyAsync(m.result.p, dres, res_bytes, hipMemcpyDeviceToHost, st));
       sync_stream(st);
     } catch (...) {
@@ -3229,7 +3339,7 @@ void Engine::run_host(const ps_scorer_desc& sc, const double* boosts, const Plan
     return;
   }
 
-  // ---- full-result mode: top_k == 0 (every match, like the reference) or top_k > 64 ----------
+  // ---- full-result mode: top_k == 0 (every match, like the reference) or top_k > PS_MAX_DEEP_TOPK ----------
   // upper bound of matches per query: min(N, sum of its list lengths)
   std::vector<uint64_t> cap(B + 1, 0);
   for (size_t q = 0; q < B; ++q) {

@@ -95,11 +95,13 @@ class Engine {
   Engine& operator=(const Engine&) = delete;
 
   // Runs one planned batch.  top_k == 0: every match (canonical order) into out/offsets.
-  // top_k  > 0: the first top_k of the canonical order per query.
+  // top_k  > 0: the first top_k of the canonical order per query (up to PS_MAX_DEEP_TOPK selected on the device and
+  // downloaded as a top-k block; beyond that the full result is sorted and cut).
   void run_host(const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t top_k,
                 ResultBuf& out, std::vector<size_t>& offsets, ps_batch_stats& stats);
-  // Device-resident top-k (1..PS_MAX_DEVICE_TOPK) into caller buffers, ordered on `stream`
-  // (nullptr = engine stream, synchronous).
+  // Device-resident top-k (1..PS_MAX_DEEP_TOPK) into caller buffers, ordered on `stream`
+  // (nullptr = engine stream, synchronous).  Above PS_MAX_DEVICE_TOPK: the deep path - runs as in full-result mode,
+  // then k_deep_select (ps_kernels_select.hpp), in slices of queries when the runs exceed PS_FULL_BUDGET_MB.
   void run_device(const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t top_k, void* d_keys,
                   void* d_scores, void* d_counts, void* stream, ps_batch_stats& stats);
 
@@ -112,7 +114,7 @@ class Engine {
   bool wants_device_plan(size_t n_queries);
   // Announce the NEXT flat BM25 batch (ps_snapshot_plan_ahead_flat): its planner count pass starts now.
   bool plan_ahead(const ps_scorer_desc& sc, const char* text, const uint64_t* offsets, size_t n_queries);
-  // false (zero_to_one only): the batch is not one K1dz takes (a query that is not simple, more than 4 lists, fewer
+  // false (top_k above PS_MAX_DEVICE_TOPK - the deep top-k path is planned on the host - and, zero_to_one only): the batch is not one K1dz takes (a query that is not simple, more than 4 lists, fewer
   // than PS_DAAT_MIN_BATCH queries ...) - nothing was enqueued, the caller plans it on the host.
   bool run_device_planned(const ps_scorer_desc& sc, const double* boosts, const char* text, const uint64_t* offsets,
                           size_t n_queries, size_t top_k, void* d_keys, void* d_scores, void* d_counts, void* stream,

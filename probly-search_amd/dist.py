@@ -212,7 +212,8 @@ def unpack_blocks(raw, world, n_queries, top_k, shard_sizes):
 def query_batch_sharded(snapshot, queries, score_calculator, fields_boost, top_k, comm=None):
     """Scores this rank's contiguous shard of `queries` on its GPU (replicated snapshot) and
     all-gathers the top-k blocks through the C ABI (ps_snapshot_query_batch_allgather_flat ->
-    ncclAllGather): every rank returns the results of the whole batch.  comm=None: one rank."""
+    ncclAllGather): every rank returns the results of the whole batch.  comm=None: one rank.
+    1 <= top_k <= 1024 (PS_MAX_DEEP_TOPK)."""
     from . import synth
     from .index import _boosts, _scorer_desc
     L = _lib.load()

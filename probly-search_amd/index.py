@@ -286,7 +286,8 @@ class Snapshot:
                            d_counts, stream=None):
         """Device-resident top-k: d_* are device pointers (ints) on this snapshot's device, e.g.
         torch tensors' data_ptr(); `stream` a hipStream_t handle (torch.cuda.Stream.cuda_stream)
-        or None for the engine's own stream (synchronous)."""
+        or None for the engine's own stream (synchronous).  1 <= top_k <= 1024 (PS_MAX_DEEP_TOPK; above 64 the
+        deep top-k path: host planner, k_deep_select on the device - same block layout)."""
         qb, arr = self._pack_queries(queries)
         desc = _scorer_desc(score_calculator)
         b, nb = _boosts(fields_boost)
