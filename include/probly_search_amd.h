@@ -146,8 +146,9 @@ int ps_device_count(void);
  * ps_update_stats, ps_query_stats ...) are written whole by the library - memset + fill, sizeof as the library was built - and grow
  * at the end between versions: a caller compiled against an older header would be written past its struct.  Compare
  * ps_abi_version() with PS_ABI_VERSION once after loading and refuse a mismatch (the Python binding does).
- * 6: ps_kernel_times.score_busy_ms (round 5), ps_comm_all_gather (round 6). */
-#define PS_ABI_VERSION 6u
+ * 6: ps_kernel_times.score_busy_ms (round 5), ps_comm_all_gather (round 6).
+ * 7: the result-page entry points (ps_snapshot_query_batch_page, .._device_page_flat, .._allgather_page_flat). */
+#define PS_ABI_VERSION 7u
 uint32_t ps_abi_version(void);
 /* Run-time options by name.  A value set here wins over the environment variable of the same name; engines read their options when
  * they are created and again at the next batch after any ps_set_option.  The list (PS_EINVAL for any other name):
@@ -319,6 +320,15 @@ ps_status ps_snapshot_query_batch(ps_snapshot* snap, const ps_scorer_desc* score
                                   size_t n_queries, const double* fields_boost, size_t n_boost,
                                   ps_tokenizer_fn tokenizer, void* user, size_t top_k, ps_result** out,
                                   size_t** out_offsets);
+/* A result page: ranks [skip, skip + top_k) of every query's canonical order - what a user of the reference takes by
+ * slicing Index::query's list.  The page is selected on the device (k_deep_window, a two-sided radix select on the deep
+ * top-k path), so n_queries x top_k records come back however deep the page lies, never the runs.  skip = 0 is
+ * ps_snapshot_query_batch.  With skip > 0: 1 <= top_k <= PS_MAX_DEEP_TOPK and skip + top_k <= 2^32 - 16, else
+ * PS_EINVAL (top_k = 0 included); the batch is unpruned for every top_k (scored into runs like a deep batch). */
+ps_status ps_snapshot_query_batch_page(ps_snapshot* snap, const ps_scorer_desc* scorer, const ps_str* queries,
+                                       size_t n_queries, const double* fields_boost, size_t n_boost,
+                                       ps_tokenizer_fn tokenizer, void* user, size_t skip, size_t top_k, ps_result** out,
+                                       size_t** out_offsets);
 
 /* Device-resident batched top-k for multi-GPU plumbing: results stay in HBM so the caller can
  * all-gather them over RCCL.  d_keys: u64[B*top_k], d_scores: f64[B*top_k], d_counts: u32[B]
@@ -364,6 +374,14 @@ ps_status ps_snapshot_query_batch_device_flat(ps_snapshot* snap, const ps_scorer
                                               const uint64_t* offsets, size_t n_queries, const double* fields_boost,
                                               size_t n_boost, ps_tokenizer_fn tokenizer, void* user, size_t top_k,
                                               void* d_keys, void* d_scores, void* d_counts, void* hip_stream);
+/* The same block for a result page: row i holds ranks [skip, skip + top_k) of query i, counts[i] = how many of them
+ * exist.  Limits as ps_snapshot_query_batch_page (1 <= top_k <= PS_MAX_DEEP_TOPK, skip + top_k <= 2^32 - 16); a batch
+ * with skip > 0 is planned on the host and takes the deep top-k path for every top_k.  skip = 0: the call above. */
+ps_status ps_snapshot_query_batch_device_page_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const char* text,
+                                                   const uint64_t* offsets, size_t n_queries, const double* fields_boost,
+                                                   size_t n_boost, ps_tokenizer_fn tokenizer, void* user, size_t skip,
+                                                   size_t top_k, void* d_keys, void* d_scores, void* d_counts,
+                                                   void* hip_stream);
 
 /* ---- multi-GPU: replicated corpus, query batch sharded across ranks, RCCL all-gather of top-k ----
  * Queries are independent (each Index::query owns its scores / visited maps, src/query.rs:31,37),
@@ -403,6 +421,13 @@ ps_status ps_snapshot_query_batch_allgather_flat(ps_snapshot* snap, ps_comm* com
                                                  const double* fields_boost, size_t n_boost, ps_tokenizer_fn tokenizer,
                                                  void* user, size_t top_k, void* d_local_block, void* d_all_blocks,
                                                  void* hip_stream);
+/* The same for a result page (every rank passes the same skip): blocks of ranks [skip, skip + top_k).  Limits as
+ * ps_snapshot_query_batch_device_page_flat; skip = 0: the call above. */
+ps_status ps_snapshot_query_batch_allgather_page_flat(ps_snapshot* snap, ps_comm* comm, const ps_scorer_desc* scorer,
+                                                      const char* text, const uint64_t* offsets, size_t n_queries,
+                                                      const double* fields_boost, size_t n_boost,
+                                                      ps_tokenizer_fn tokenizer, void* user, size_t skip, size_t top_k,
+                                                      void* d_local_block, void* d_all_blocks, void* hip_stream);
 
 /* SURVEY 8f N2 - the same batch call with the PLANNER on the device too: tokenising (split on ' '),
  * term lookup in the frozen trie, prefix expansion in the reference's newest-first DFS order

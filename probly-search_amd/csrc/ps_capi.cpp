@@ -142,7 +142,7 @@ std::vector<std::string_view> views_of(const ps_str* queries, size_t n) {
 static ps_status run_device_views(ps_snapshot* snap, const ps_scorer_desc* scorer,
                                   const std::vector<std::string_view>& qs, const double* fields_boost, size_t n_boost,
                                   ps_tokenizer_fn tokenizer, void* user, size_t top_k, void* d_keys, void* d_scores,
-                                  void* d_counts, void* hip_stream) {
+                                  void* d_counts, void* hip_stream, size_t skip = 0) {
   ps_status st = check_query_args(snap, scorer, fields_boost, n_boost);
   if (st != PS_OK) return st;
   if (!d_keys || !d_scores || !d_counts) return fail(PS_EINVAL, "null argument");
@@ -151,7 +151,7 @@ static ps_status run_device_views(ps_snapshot* snap, const ps_scorer_desc* score
   plan_batch(snap, *scorer, qs, tokenizer, user, plan);
   const double t1 = wall_ms();
   ps_batch_stats stats;
-  snap->engine->run_device(*scorer, fields_boost, plan, top_k, d_keys, d_scores, d_counts, hip_stream, stats);
+  snap->engine->run_device(*scorer, fields_boost, plan, top_k, d_keys, d_scores, d_counts, hip_stream, stats, skip);
   stats.plan_ms = t1 - t0;
   stats.total_ms = wall_ms() - t0;
   set_stats(snap, stats);
@@ -163,13 +163,15 @@ ps_status set_error(ps_status st, const char* msg) { return fail(st, msg); }
 
 ps_status run_device_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const char* text, const uint64_t* offsets,
                           size_t n_queries, const double* fields_boost, size_t n_boost, ps_tokenizer_fn tokenizer,
-                          void* user, size_t top_k, void* d_keys, void* d_scores, void* d_counts, void* hip_stream) {
+                          void* user, size_t top_k, void* d_keys, void* d_scores, void* d_counts, void* hip_stream,
+                          size_t skip) {
   return guard([&]() -> ps_status {
     if (n_queries && (!text || !offsets)) return fail(PS_EINVAL, "null argument");
     // BM25 top-k batches with the built-in tokenizer are planned on the device too (k_plan): the host
     // hands the text over and sizes the launches from the plan's totals
     // (zero_to_one: the batches K1dz takes; run_device_planned hands the others back before anything is enqueued)
-    if (!tokenizer && snap && scorer && (scorer->kind == PS_SCORER_BM25 || scorer->kind == PS_SCORER_ZERO_TO_ONE) && snap->engine &&
+    // (a result page, skip > 0, is planned on the host like any deep batch)
+    if (!skip && !tokenizer && snap && scorer && (scorer->kind == PS_SCORER_BM25 || scorer->kind == PS_SCORER_ZERO_TO_ONE) && snap->engine &&
         top_k >= 1 && top_k <= PS_MAX_DEVICE_TOPK && offsets && snap->engine->wants_device_plan(n_queries)) {
       ps_status st = check_query_args(snap, scorer, fields_boost, n_boost);
       if (st != PS_OK) return st;
@@ -186,7 +188,7 @@ ps_status run_device_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const
     std::vector<std::string_view> qs(n_queries);
     for (size_t i = 0; i < n_queries; ++i) qs[i] = std::string_view(text + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
     return run_device_views(snap, scorer, qs, fields_boost, n_boost, tokenizer, user, top_k, d_keys, d_scores, d_counts,
-                            hip_stream);
+                            hip_stream, skip);
   });
 }
 }  // namespace ps
@@ -532,7 +534,7 @@ ps_status ps_snapshot_get_info(const ps_snapshot* snap, ps_snapshot_info* out) {
 
 static ps_status run_batch(ps_snapshot* snap, const ps_scorer_desc* scorer, const ps_str* queries, size_t n,
                            const double* fields_boost, size_t n_boost, ps_tokenizer_fn tokenizer, void* user,
-                           size_t top_k, ps_result** out, size_t** out_offsets) {
+                           size_t skip, size_t top_k, ps_result** out, size_t** out_offsets) {
   return guard([&]() -> ps_status {
     ps_status st = check_query_args(snap, scorer, fields_boost, n_boost);
     if (st != PS_OK) return st;
@@ -544,7 +546,7 @@ static ps_status run_batch(ps_snapshot* snap, const ps_scorer_desc* scorer, cons
     ps::ResultBuf res;  // (a malloc'd block, handed to the caller as it is)
     std::vector<size_t> offs;
     ps_batch_stats stats;
-    snap->engine->run_host(*scorer, fields_boost, plan, top_k, res, offs, stats);
+    snap->engine->run_host(*scorer, fields_boost, plan, top_k, res, offs, stats, skip);
     stats.plan_ms = t1 - t0;
     stats.total_ms = wall_ms() - t0;
     set_stats(snap, stats);
@@ -561,7 +563,14 @@ ps_status ps_snapshot_query_batch(ps_snapshot* snap, const ps_scorer_desc* score
                                   size_t n_queries, const double* fields_boost, size_t n_boost,
                                   ps_tokenizer_fn tokenizer, void* user, size_t top_k, ps_result** out,
                                   size_t** out_offsets) {
-  return run_batch(snap, scorer, queries, n_queries, fields_boost, n_boost, tokenizer, user, top_k, out, out_offsets);
+  return run_batch(snap, scorer, queries, n_queries, fields_boost, n_boost, tokenizer, user, 0, top_k, out, out_offsets);
+}
+
+ps_status ps_snapshot_query_batch_page(ps_snapshot* snap, const ps_scorer_desc* scorer, const ps_str* queries,
+                                       size_t n_queries, const double* fields_boost, size_t n_boost,
+                                       ps_tokenizer_fn tokenizer, void* user, size_t skip, size_t top_k, ps_result** out,
+                                       size_t** out_offsets) {
+  return run_batch(snap, scorer, queries, n_queries, fields_boost, n_boost, tokenizer, user, skip, top_k, out, out_offsets);
 }
 
 ps_status ps_snapshot_query(ps_snapshot* snap, const ps_scorer_desc* scorer, const char* query, size_t query_len,
@@ -570,7 +579,7 @@ ps_status ps_snapshot_query(ps_snapshot* snap, const ps_scorer_desc* scorer, con
   if (!out || !out_len) return fail(PS_EINVAL, "null argument");
   ps_str q{query, query_len};
   size_t* offs = nullptr;
-  ps_status st = run_batch(snap, scorer, &q, 1, fields_boost, n_boost, tokenizer, user, top_k, out, &offs);
+  ps_status st = run_batch(snap, scorer, &q, 1, fields_boost, n_boost, tokenizer, user, 0, top_k, out, &offs);
   if (st != PS_OK) return st;
   *out_len = offs[1];
   free(offs);
@@ -640,6 +649,15 @@ ps_status ps_snapshot_query_batch_device_flat(ps_snapshot* snap, const ps_scorer
                                               void* d_keys, void* d_scores, void* d_counts, void* hip_stream) {
   return ps::run_device_flat(snap, scorer, text, offsets, n_queries, fields_boost, n_boost, tokenizer, user, top_k, d_keys,
                              d_scores, d_counts, hip_stream);
+}
+
+ps_status ps_snapshot_query_batch_device_page_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const char* text,
+                                                   const uint64_t* offsets, size_t n_queries, const double* fields_boost,
+                                                   size_t n_boost, ps_tokenizer_fn tokenizer, void* user, size_t skip,
+                                                   size_t top_k, void* d_keys, void* d_scores, void* d_counts,
+                                                   void* hip_stream) {
+  return ps::run_device_flat(snap, scorer, text, offsets, n_queries, fields_boost, n_boost, tokenizer, user, top_k, d_keys,
+                             d_scores, d_counts, hip_stream, skip);
 }
 
 ps_status ps_snapshot_query_batch_device_planned_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const char* text,

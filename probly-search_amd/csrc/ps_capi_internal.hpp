@@ -21,9 +21,10 @@ struct ps_snapshot {
 };
 
 namespace ps {
-// Plans `n_queries` flat queries and enqueues the batch on `hip_stream` (ps_capi.cpp).
+// Plans `n_queries` flat queries and enqueues the batch on `hip_stream` (ps_capi.cpp); skip > 0: a result page.
 ps_status run_device_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const char* text, const uint64_t* offsets,
                           size_t n_queries, const double* fields_boost, size_t n_boost, ps_tokenizer_fn tokenizer,
-                          void* user, size_t top_k, void* d_keys, void* d_scores, void* d_counts, void* hip_stream);
+                          void* user, size_t top_k, void* d_keys, void* d_scores, void* d_counts, void* hip_stream,
+                          size_t skip = 0);
 ps_status set_error(ps_status st, const char* msg);
 }  // namespace ps

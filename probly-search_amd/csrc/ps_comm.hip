@@ -329,12 +329,21 @@ ps_status ps_snapshot_query_batch_allgather_flat(ps_snapshot* snap, ps_comm* com
                                                  const double* fields_boost, size_t n_boost, ps_tokenizer_fn tokenizer,
                                                  void* user, size_t top_k, void* d_local_block, void* d_all_blocks,
                                                  void* hip_stream) {
+  return ps_snapshot_query_batch_allgather_page_flat(snap, comm, scorer, text, offsets, n_queries, fields_boost, n_boost,
+                                                     tokenizer, user, 0, top_k, d_local_block, d_all_blocks, hip_stream);
+}
+
+ps_status ps_snapshot_query_batch_allgather_page_flat(ps_snapshot* snap, ps_comm* comm, const ps_scorer_desc* scorer,
+                                                      const char* text, const uint64_t* offsets, size_t n_queries,
+                                                      const double* fields_boost, size_t n_boost,
+                                                      ps_tokenizer_fn tokenizer, void* user, size_t skip, size_t top_k,
+                                                      void* d_local_block, void* d_all_blocks, void* hip_stream) {
   if (!d_local_block || !d_all_blocks) return ps::set_error(PS_EINVAL, "null block pointer");
   unsigned char* blk = (unsigned char*)d_local_block;
   const size_t nk = n_queries * top_k;
   // scoring: no collective (queries are independent); ordered on the caller's stream
   ps_status st = ps::run_device_flat(snap, scorer, text, offsets, n_queries, fields_boost, n_boost, tokenizer, user, top_k,
-                                     blk, blk + nk * 8, blk + nk * 16, hip_stream);
+                                     blk, blk + nk * 8, blk + nk * 16, hip_stream, skip);
   if (st != PS_OK) return st;
   return ps_comm_all_gather(comm, d_local_block, d_all_blocks, ps_topk_block_bytes(n_queries, top_k), hip_stream);
 }

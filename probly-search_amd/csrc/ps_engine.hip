@@ -2741,8 +2741,10 @@ Plan sub_plan(const Plan& plan, size_t b, size_t e) {
 // a run longer than the LDS candidate buffer brings the same size of scratch again).  Enqueueing is not free of waits
 // with many slices: every slice stages its sub-plan in a pinned slot and takes a timer from the ring, and once
 // either ring wraps (N_STAGE slots, N_KTIMER timers) the host waits for the event of the slice that last used the entry.
-void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t top_k, void* d_keys,
-                  void* d_scores, void* d_counts, hipStream_t st) {
+// skip > 0 (a result page, any top_k in [1, PS_MAX_DEEP_TOPK]): K4w k_deep_window instead, ranks [skip, skip + top_k)
+// of every run; everything in front of the select is the same.
+void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t skip, size_t top_k,
+                  void* d_keys, void* d_scores, void* d_counts, hipStream_t st) {
   const Snapshot& s = *m.snap;
   const size_t B = plan.qbeg.size() - 1;
   refresh_tuning(m);
@@ -2781,7 +2783,7 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
     m.d_sort_doc.ensure(max_cap + 1);
     m.d_sort_score.ensure(max_cap + 1);
   }
-  allow_lds(reinterpret_cast<const void*>(&k_deep_select), DEEP_LDS);
+  allow_lds(skip ? reinterpret_cast<const void*>(&k_deep_window) : reinterpret_cast<const void*>(&k_deep_select), DEEP_LDS);
   for (size_t i = 0; i + 1 < cut.size(); ++i) {
     const size_t qa = cut[i], qb = cut[i + 1], nq = qb - qa;
     const bool whole = nq == B;
@@ -2826,7 +2828,8 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
     dp.out_counts = static_cast<uint32_t*>(d_counts);
     dp.K = (uint32_t)top_k;
     dp.row0 = (uint32_t)qa;
-    hipLaunchKernelGGL(k_deep_select, dim3((uint32_t)nq), dim3(DEEP_NT), DEEP_LDS, st, dp);
+    if (skip) hipLaunchKernelGGL(k_deep_window, dim3((uint32_t)nq), dim3(DEEP_NT), DEEP_LDS, st, dp, (uint32_t)skip);
+    else hipLaunchKernelGGL(k_deep_select, dim3((uint32_t)nq), dim3(DEEP_NT), DEEP_LDS, st, dp);
     PS_HIP(hipGetLastError());
     if (m.cur_zero_copy) {  // stage 1 reads the staging slot in place: fence it
       PS_HIP(hipEventRecord(m.cur_stage->done, st));
@@ -2837,6 +2840,13 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
   PS_HIP(hipEventRecord(m.ev[0], st));
   m.tail_stream = st;
   m.tail_pending = true;
+}
+
+// A result page (skip > 0) is selected on the device for 1 <= top_k <= PS_MAX_DEEP_TOPK only (k_deep_window).
+void check_page(size_t skip, size_t top_k) {
+  if (!skip) return;
+  if (top_k < 1 || top_k > PS_MAX_DEEP_TOPK) throw std::invalid_argument("top_k must be in [1, 1024] with skip > 0");
+  if (skip > 0xFFFFFFF0ull - top_k) throw std::invalid_argument("skip + top_k must be at most 2^32 - 16");
 }
 
 }  // namespace
@@ -3264,17 +3274,18 @@ bool Engine::run_device_planned(const ps_scorer_desc& sc, const double* boosts, 
 }
 
 void Engine::run_device(const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t top_k, void* d_keys,
-                        void* d_scores, void* d_counts, void* stream, ps_batch_stats& stats) {
+                        void* d_scores, void* d_counts, void* stream, ps_batch_stats& stats, size_t skip) {
   EngineImpl& m = *impl_;
   const Snapshot& s = *m.snap;
   validate(s, sc, plan);
   if (top_k < 1 || top_k > PS_MAX_DEEP_TOPK)
     throw std::invalid_argument("top_k must be in [1, 1024] for the device top-k path");
+  check_page(skip, top_k);
   std::lock_guard<std::mutex> lock(m.mu);
   PS_HIP(hipSetDevice(m.device));
   const double t0 = now_ms();
   hipStream_t st = stream ? (hipStream_t)stream : m.stream;
-  if (top_k > PS_MAX_DEVICE_TOPK) enqueue_deep(m, sc, boosts, plan, top_k, d_keys, d_scores, d_counts, st);
+  if (skip || top_k > PS_MAX_DEVICE_TOPK) enqueue_deep(m, sc, boosts, plan, skip, top_k, d_keys, d_scores, d_counts, st);
   else enqueue_topk(m, sc, boosts, plan, top_k, d_keys, d_scores, d_counts, st, false);
   memset(&stats, 0, sizeof(stats));
   fill_stats(m, stats, s, plan, (uint64_t)(plan.qbeg.size() - 1) * top_k);
@@ -3286,18 +3297,20 @@ void Engine::run_device(const ps_scorer_desc& sc, const double* boosts, const Pl
 }
 
 void Engine::run_host(const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t top_k,
-                      ResultBuf& out, std::vector<size_t>& offsets, ps_batch_stats& stats) {
+                      ResultBuf& out, std::vector<size_t>& offsets, ps_batch_stats& stats, size_t skip) {
   EngineImpl& m = *impl_;
   const Snapshot& s = *m.snap;
   const size_t B = plan.qbeg.size() - 1;
   validate(s, sc, plan);
+  check_page(skip, top_k);
   out.clear();
   offsets.assign(B + 1, 0);
   memset(&stats, 0, sizeof(stats));
   const double t0 = now_ms();
 
   if (top_k >= 1 && top_k <= PS_MAX_DEEP_TOPK) {
-    const bool deep = top_k > PS_MAX_DEVICE_TOPK;  // k_deep_select instead of the scoring kernels' own top-k: the same block
+    // k_deep_select (a page: k_deep_window) instead of the scoring kernels' own top-k: the same block
+    const bool deep = skip || top_k > PS_MAX_DEVICE_TOPK;
     std::lock_guard<std::mutex> lock(m.mu);
     PS_HIP(hipSetDevice(m.device));
     hipStream_t st = m.stream;
@@ -3315,7 +3328,7 @@ void Engine::run_host(const ps_scorer_desc& sc, const double* boosts, const Plan
       dres = reinterpret_cast<unsigned char*>(m.d_out_keys.p);
     }
     try {
-      if (deep) enqueue_deep(m, sc, boosts, plan, top_k, dres, dres + nb * 8, dres + nb * 16, st);
+      if (deep) enqueue_deep(m, sc, boosts, plan, skip, top_k, dres, dres + nb * 8, dres + nb * 16, st);
       else enqueue_topk(m, sc, boosts, plan, top_k, dres, dres + nb * 8, dres + nb * 16, st, true);
       if (!direct && res_bytes) PS_HIP(hipMemcpyAsync(m.result.p, dres, res_bytes, hipMemcpyDeviceToHost, st));
       sync_stream(st);

@@ -98,12 +98,14 @@ class Engine {
   // top_k  > 0: the first top_k of the canonical order per query (up to PS_MAX_DEEP_TOPK selected on the device and
   // downloaded as a top-k block; beyond that the full result is sorted and cut).
   void run_host(const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t top_k,
-                ResultBuf& out, std::vector<size_t>& offsets, ps_batch_stats& stats);
+                ResultBuf& out, std::vector<size_t>& offsets, ps_batch_stats& stats, size_t skip = 0);
   // Device-resident top-k (1..PS_MAX_DEEP_TOPK) into caller buffers, ordered on `stream`
   // (nullptr = engine stream, synchronous).  Above PS_MAX_DEVICE_TOPK: the deep path - runs as in full-result mode,
   // then k_deep_select (ps_kernels_select.hpp), in slices of queries when the runs exceed PS_FULL_BUDGET_MB.
+  // skip > 0 (both entries): ranks [skip, skip + top_k) instead of the first top_k - a result page, selected by
+  // k_deep_window on that same path for every top_k in [1, PS_MAX_DEEP_TOPK]; skip + top_k <= 2^32 - 16.
   void run_device(const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t top_k, void* d_keys,
-                  void* d_scores, void* d_counts, void* stream, ps_batch_stats& stats);
+                  void* d_scores, void* d_counts, void* stream, ps_batch_stats& stats, size_t skip = 0);
 
   // SURVEY 8f N2 - device-side planner (BM25 and zero_to_one, built-in tokenizer): tokenise, term lookup in the frozen
   // trie, prefix expansion and before_each run on the GPU.  plan_device copies the plan back (tests);

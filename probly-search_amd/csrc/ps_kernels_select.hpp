@@ -1,4 +1,5 @@
-// ps_kernels_select.hpp — deep top-k (64 < K <= PS_MAX_DEEP_TOPK): k_deep_offsets + K4s k_deep_select.
+// ps_kernels_select.hpp — deep top-k (64 < K <= PS_MAX_DEEP_TOPK): k_deep_offsets + K4s k_deep_select, and result
+// pages (ranks [skip, skip + K) for skip > 0): K4w k_deep_window, a two-sided form of the same select (at the end).
 //
 // Stage 1 is full-result mode's (k_score<.., FULL> / k_z21<true>): every query's run of (doc, score) behind
 // full_off / full_cnt.  k_deep_select then picks the first K of the run's canonical order (score desc, doc asc)
@@ -103,8 +104,8 @@ struct Prefix {  // the pivot digits so far: an element is still a candidate whi
   }
 };
 
-struct Ctl {  // LDS control words
-  uint32_t n_win, n_dst, pivot, above, pop;
+struct Ctl {  // LDS control words (pivot2 .. pop2: the second target of k_deep_window's two-sided descent)
+  uint32_t n_win, n_dst, pivot, above, pop, pivot2, above2, pop2;
   uint32_t wave_tot[DEEP_WAVES];
 };
 
@@ -135,11 +136,14 @@ __device__ __forceinline__ uint32_t wave_slot(uint32_t* counter, const int lane,
 // One pass over src[0, m): of the elements that match `pre`,
 //   sel_lvl >= 0: digit > pivot -> winners, digit < pivot -> dropped, digit == pivot -> kept (take_pivot: winners too);
 //   kept elements go to dst (when there is one; dst_cap elements) and into the histogram of hist_lvl (when >= 0).
+// k_deep_window's two additions: digits are taken XOR `flip` (0, or DEEP_BINS - 1: the order mirrored, so that the
+// same descent selects from the bottom), and a digit above `top` is dropped instead of won (the window's upper side).
 // Every thread of the workgroup calls with the same arguments.
 __device__ __forceinline__ void select_pass(const uint64_t* src_s, const uint32_t* src_d, const uint64_t m, const Prefix pre,
                                             const int sel_lvl, const uint32_t pivot, const bool take_pivot, const int hist_lvl,
                                             uint64_t* dst_s, uint32_t* dst_d, const uint32_t dst_cap, uint32_t* hist,
-                                            uint64_t* win_s, uint32_t* win_d, Ctl* ctl) {
+                                            uint64_t* win_s, uint32_t* win_d, Ctl* ctl, const uint32_t flip = 0u,
+                                            const uint32_t top = ~0u) {
   const int lane = threadIdx.x & (WAVE - 1);
   const Level gs = level_of(sel_lvl < 0 ? 0 : sel_lvl), gh = level_of(hist_lvl < 0 ? 0 : hist_lvl);
   // the doc id is only fetched by a pass that looks at it or moves it
@@ -159,8 +163,8 @@ __device__ __forceinline__ void select_pass(const uint64_t* src_s, const uint32_
       const bool act = i < m && (s[u] & pre.s_mask) == pre.s_val && (nd[u] & pre.d_mask) == pre.d_val;
       bool win = false, keep = act;
       if (sel_lvl >= 0) {
-        const uint32_t dg = digit_of(gs, s[u], nd[u]);
-        win = act && (dg > pivot || (take_pivot && dg == pivot));
+        const uint32_t dg = digit_of(gs, s[u], nd[u]) ^ flip;
+        win = act && (dg > pivot || (take_pivot && dg == pivot)) && dg <= top;
         keep = act && dg == pivot && !take_pivot;
         const uint32_t w = wave_slot(&ctl->n_win, lane, win);
         if (win && w < (uint32_t)DEEP_MAX_K) { win_s[w] = s[u]; win_d[w] = ~nd[u]; }
@@ -169,14 +173,15 @@ __device__ __forceinline__ void select_pass(const uint64_t* src_s, const uint32_
         const uint32_t o = wave_slot(&ctl->n_dst, lane, keep);
         if (keep && o < dst_cap) { dst_s[o] = s[u]; dst_d[o] = ~nd[u]; }
       }
-      if (hist_lvl >= 0) hist_add(hist, lane, keep, digit_of(gh, s[u], nd[u]));
+      if (hist_lvl >= 0) hist_add(hist, lane, keep, digit_of(gh, s[u], nd[u]) ^ flip);
     }
   }
 }
 
 // The pivot bin of the histogram for `need` elements from the top: ctl->pivot, ->above (elements in higher bins),
-// ->pop (elements in it).  need >= 1 and the histogram holds at least `need`.  Ends with a barrier.
-__device__ __forceinline__ void find_pivot(const uint32_t* hist, const uint32_t need, Ctl* ctl) {
+// ->pop (elements in it) - or ->pivot2, ->above2, ->pop2 for `second`.  need >= 1 and the histogram holds at least
+// `need`.  Ends with a barrier.
+__device__ __forceinline__ void find_pivot(const uint32_t* hist, const uint32_t need, Ctl* ctl, const bool second = false) {
   constexpr int PER = DEEP_BINS / DEEP_NT;
   const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
   const int top = DEEP_BINS - 1 - (int)threadIdx.x * PER;  // this thread's bins: top, top - 1, ... (descending digits)
@@ -195,7 +200,10 @@ __device__ __forceinline__ void find_pivot(const uint32_t* hist, const uint32_t 
   if (above < need && need - above <= mine) {  // the crossing lies in this thread's bins
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
-      if (above < need && need - above <= h[j]) { ctl->pivot = (uint32_t)(top - j); ctl->above = above; ctl->pop = h[j]; }
+      if (above < need && need - above <= h[j]) {
+        if (second) { ctl->pivot2 = (uint32_t)(top - j); ctl->above2 = above; ctl->pop2 = h[j]; }
+        else { ctl->pivot = (uint32_t)(top - j); ctl->above = above; ctl->pop = h[j]; }
+      }
       above += h[j];
     }
   }
@@ -204,6 +212,36 @@ __device__ __forceinline__ void find_pivot(const uint32_t* hist, const uint32_t 
 
 __device__ __forceinline__ void clear_hist(uint32_t* hist) {
   for (int b = threadIdx.x; b < DEEP_BINS; b += DEEP_NT) hist[b] = 0u;
+}
+
+// The end of both select kernels: bitonic sort of the n_win winners (LDS), padded to a power of two with keys below
+// every real one, then row row0 + q of the caller's block: winners [first, first + n_out), padding, the count.
+__device__ __forceinline__ void sort_and_write(const DeepParams& a, const uint32_t q, uint64_t* win_s, uint32_t* win_d,
+                                               const uint32_t n_win, const uint32_t first, const uint32_t n_out) {
+  const uint32_t K = a.K;
+  uint32_t P = 1;
+  while (P < n_win) P <<= 1;
+  for (uint32_t i = n_win + threadIdx.x; i < P; i += DEEP_NT) { win_s[i] = 0ull; win_d[i] = 0xFFFFFFFFu; }
+  __syncthreads();
+  for (uint32_t k = 2; k <= P; k <<= 1) {
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      const uint32_t i = threadIdx.x, x = i ^ j;
+      if (i < P && x > i) {
+        const uint64_t si = win_s[i], sx = win_s[x];
+        const uint32_t di = win_d[i], dx = win_d[x];
+        const bool i_first = si > sx || (si == sx && di < dx);  // canonical order: score desc, doc asc
+        if (((i & k) == 0) != i_first) { win_s[i] = sx; win_d[i] = dx; win_s[x] = si; win_d[x] = di; }
+      }
+      __syncthreads();
+    }
+  }
+  const uint64_t row = (uint64_t)(a.row0 + q) * K;
+  for (uint32_t i = threadIdx.x; i < K; i += DEEP_NT) {
+    const bool ok = i < n_out;
+    a.out_keys[row + i] = ok ? a.keys[win_d[first + i]] : ~0ull;
+    a.out_scores[row + i] = ok ? __longlong_as_double((long long)win_s[first + i]) : 0.0;
+  }
+  if (threadIdx.x == 0) a.out_counts[a.row0 + q] = n_out;
 }
 
 }  // namespace deep
@@ -271,31 +309,150 @@ __global__ __launch_bounds__(DEEP_NT) void k_deep_select(const DeepParams a) {
   }
   __syncthreads();
   if (n > K) n_out = min(K, ctl->n_win);  // (== K: the winners are exactly the K largest keys)
+  sort_and_write(a, q, win_s, win_d, n_out, 0u, n_out);
+}
 
-  // bitonic sort of the winners, padded to a power of two with keys below every real one
-  uint32_t P = 1;
-  while (P < n_out) P <<= 1;
-  for (uint32_t i = n_out + threadIdx.x; i < P; i += DEEP_NT) { win_s[i] = 0ull; win_d[i] = 0xFFFFFFFFu; }
+// K4w: ranks [skip, skip + K) of every run's canonical order (a result page) into the same block; skip > 0.
+// With lo = skip and hi = min(n, skip + K):
+//   lo >= n            padding only;
+//   n <= DEEP_MAX_K    the whole run is sorted in LDS and [lo, hi) of it written;
+//   hi <= DEEP_MAX_K   k_deep_select's one-sided descent for the top hi, then [lo, hi) of the sorted winners;
+//   hi >  DEEP_MAX_K   a two-sided descent: what lies above the window is unbounded and is never collected.
+// The two-sided descent is ONE loop over the levels in three roles.  TRUNK: both targets (rank lo and rank hi - 1)
+// are looked up in the same histogram; while they fall into the same bin the pass keeps that bin only (no winners)
+// and compacts it by k_deep_select's rules.  PARTING level: the bins strictly between the two pivot bins are winners
+// outright (their ranks lie inside the window), a boundary bin that lies wholly inside is too; nothing is compacted
+// here - both tails start from where the trunk left the candidates (a trunk that reached LDS serves both from LDS).
+// TAILS: the lower boundary bin gives its highest hi - above_hi elements - a one-sided descent as in k_deep_select,
+// whose first histogram the parting pass made -, then the upper boundary bin gives its lowest above_lo + pop_lo - lo:
+// the same descent over mirrored digits (flip), after one counting pass of its own.  While the upper tail waits, the
+// lower one must not compact into the global buffer the trunk's candidates are in (it may use the other one, once).
+// Passes over a run of distinct scores: k_deep_select's own when the targets part after the candidates reached LDS
+// (parting, tails and the counting pass then work in LDS); when they part while the candidates are still a global
+// buffer, up to three more over that buffer - the parting pass (wins and counts, does not compact), the lower tail's
+// first pass and the upper tail's counting pass - before each tail has compacted its bin.  DESIGN.md section 3.
+__global__ __launch_bounds__(DEEP_NT) void k_deep_window(const DeepParams a, const uint32_t skip) {
+  using namespace deep;
+  extern __shared__ __align__(16) unsigned char deep_lds[];
+  uint32_t* hist = reinterpret_cast<uint32_t*>(deep_lds);
+  uint64_t* cand_s = reinterpret_cast<uint64_t*>(deep_lds + (size_t)DEEP_BINS * 4);
+  uint64_t* win_s = cand_s + DEEP_CAND;
+  uint32_t* cand_d = reinterpret_cast<uint32_t*>(win_s + DEEP_MAX_K);
+  uint32_t* win_d = cand_d + DEEP_CAND;
+  Ctl* ctl = reinterpret_cast<Ctl*>(win_d + DEEP_MAX_K);
+
+  const uint32_t q = blockIdx.x, K = a.K;
+  const uint64_t off = a.off[q];
+  const uint64_t n = min((uint64_t)a.cnt[q], a.off[q + 1] - off);
+  const uint64_t hi = min(n, (uint64_t)skip + K);
+  const uint32_t n_out = skip < n ? (uint32_t)(hi - skip) : 0u;
+  uint32_t n_win = 0, first = 0;  // winners to sort; where the window begins among them
+  if (threadIdx.x == 0) { ctl->n_win = 0; ctl->n_dst = 0; }
+  clear_hist(hist);
   __syncthreads();
-  for (uint32_t k = 2; k <= P; k <<= 1) {
-    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-      const uint32_t i = threadIdx.x, x = i ^ j;
-      if (i < P && x > i) {
-        const uint64_t si = win_s[i], sx = win_s[x];
-        const uint32_t di = win_d[i], dx = win_d[x];
-        const bool i_first = si > sx || (si == sx && di < dx);  // canonical order: score desc, doc asc
-        if (((i & k) == 0) != i_first) { win_s[i] = sx; win_d[i] = dx; win_s[x] = si; win_d[x] = di; }
+
+  if (n_out == 0) {  // the page lies behind the run
+  } else if (n <= (uint64_t)DEEP_MAX_K) {
+    for (uint32_t i = threadIdx.x; i < (uint32_t)n; i += DEEP_NT) { win_s[i] = a.run_score[off + i]; win_d[i] = a.run_doc[off + i]; }
+    n_win = (uint32_t)n;
+    first = skip;
+  } else {
+    const bool two_sided = hi > (uint64_t)DEEP_MAX_K;
+    const uint64_t* src_s = a.run_score + off;
+    const uint32_t* src_d = a.run_doc + off;
+    uint64_t m = n;
+    bool in_lds = false, in_tmp = false;
+    Prefix pre;
+    bool trunk = two_sided;
+    uint32_t t_lo = skip + 1u, t_hi = (uint32_t)hi;  // the targets, counted from the top of the candidates (a tail has t_hi only)
+    uint32_t flip = 0u;
+    // the upper tail while the lower one runs: its prefix, level, count, and the trunk's candidates
+    bool up_waits = false, up_in_lds = false, up_in_tmp = false;
+    Prefix up_pre;
+    int up_lvl = 0;
+    uint32_t up_need = 0u;
+    const uint64_t* up_src_s = nullptr;
+    const uint32_t* up_src_d = nullptr;
+    uint64_t up_m = 0;
+    bool count_first = true;  // the histogram of `lvl` is still to be made
+    for (int lvl = 0;;) {
+      if (count_first) {
+        if (in_lds) select_pass(cand_s, cand_d, m, pre, -1, 0u, false, lvl, nullptr, nullptr, 0u, hist, win_s, win_d, ctl, flip);
+        else select_pass(src_s, src_d, m, pre, -1, 0u, false, lvl, nullptr, nullptr, 0u, hist, win_s, win_d, ctl, flip);
+        __syncthreads();
+        count_first = false;
       }
+      uint32_t pivot, pop, top = ~0u, up_pivot = 0u;
+      bool last, part = false;
+      if (trunk) {
+        find_pivot(hist, t_lo, ctl);
+        find_pivot(hist, t_hi, ctl, true);
+        const uint32_t p_lo = ctl->pivot, above_lo = ctl->above, pop_lo = ctl->pop;
+        const uint32_t p_hi = ctl->pivot2, above_hi = ctl->above2, pop_hi = ctl->pop2;
+        if (p_lo == p_hi) {  // one bin holds the window: keep it, win nothing - unless it IS the window
+          pivot = p_lo; pop = pop_lo; top = p_lo;
+          t_lo -= above_lo;
+          t_hi -= above_lo;
+          last = (t_lo == 1u && t_hi == pop_lo) || lvl == DEEP_LEVELS - 1;
+        } else {  // the targets part (p_lo > p_hi)
+          part = true;
+          const uint32_t c_lo = above_lo + pop_lo - (t_lo - 1u), c_hi = t_hi - above_hi;  // what the boundary bins contribute
+          up_waits = c_lo != pop_lo;
+          up_pivot = p_lo; up_need = c_lo;
+          pivot = p_hi; pop = pop_hi; top = up_waits ? p_lo - 1u : p_lo;
+          t_hi = c_hi;
+          last = c_hi == pop_hi;
+        }
+      } else {
+        find_pivot(hist, t_hi, ctl);
+        pivot = ctl->pivot; pop = ctl->pop;
+        t_hi -= ctl->above;
+        last = pop == t_hi || lvl == DEEP_LEVELS - 1;
+      }
+      uint64_t* const glb_s = (in_tmp ? a.run_score : a.tmp_score) + off;  // the global buffer the source is not in
+      uint32_t* const glb_d = (in_tmp ? a.run_doc : a.tmp_doc) + off;
+      const bool may_move = !last && !part && !in_lds;
+      const bool to_lds = may_move && pop <= (uint32_t)DEEP_CAND;
+      const bool to_glb = may_move && !to_lds && (uint64_t)pop <= m / 2 && !(up_waits && glb_s == up_src_s);
+      __syncthreads();  // every thread has read ctl and the histogram
+      clear_hist(hist);
+      if (threadIdx.x == 0) ctl->n_dst = 0;
       __syncthreads();
+      const int hist_lvl = last ? -1 : lvl + 1;
+      if (in_lds) {
+        select_pass(cand_s, cand_d, m, pre, lvl, pivot, last, hist_lvl, nullptr, nullptr, 0u, hist, win_s, win_d, ctl, flip, top);
+      } else {
+        select_pass(src_s, src_d, m, pre, lvl, pivot, last, hist_lvl, to_lds ? cand_s : to_glb ? glb_s : nullptr,
+                    to_lds ? cand_d : to_glb ? glb_d : nullptr, pop, hist, win_s, win_d, ctl, flip, top);
+      }
+      if (part) {  // the trunk ends: its candidates stay where they are for the upper tail
+        up_pre = pre;
+        up_pre.push(level_of(lvl), up_pivot);
+        up_lvl = lvl + 1;
+        up_src_s = src_s; up_src_d = src_d; up_m = m; up_in_lds = in_lds; up_in_tmp = in_tmp;
+        trunk = false;
+      }
+      if (to_glb) { src_s = glb_s; src_d = glb_d; in_tmp = !in_tmp; }
+      if (to_lds || to_glb) m = pop;
+      if (to_lds) in_lds = true;
+      pre.push(level_of(lvl), pivot ^ flip);
+      ++lvl;
+      __threadfence_block();
+      __syncthreads();  // (a global destination is read back by this workgroup only)
+      if (last) {  // this descent is complete
+        if (!up_waits) break;
+        up_waits = false;
+        pre = up_pre; lvl = up_lvl; t_hi = up_need;
+        src_s = up_src_s; src_d = up_src_d; m = up_m; in_lds = up_in_lds; in_tmp = up_in_tmp;
+        flip = (uint32_t)DEEP_BINS - 1u;
+        count_first = true;
+      }
     }
+    n_win = min((uint32_t)DEEP_MAX_K, ctl->n_win);  // (== hi one-sided, == hi - lo two-sided: keys are unique)
+    first = two_sided ? 0u : skip;
   }
-  const uint64_t row = (uint64_t)(a.row0 + q) * K;
-  for (uint32_t i = threadIdx.x; i < K; i += DEEP_NT) {
-    const bool ok = i < n_out;
-    a.out_keys[row + i] = ok ? a.keys[win_d[i]] : ~0ull;
-    a.out_scores[row + i] = ok ? __longlong_as_double((long long)win_s[i]) : 0.0;
-  }
-  if (threadIdx.x == 0) a.out_counts[a.row0 + q] = n_out;
+  __syncthreads();
+  sort_and_write(a, q, win_s, win_d, n_win, first, n_out);
 }
 
 }  // namespace ps

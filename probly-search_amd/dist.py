@@ -209,11 +209,12 @@ def unpack_blocks(raw, world, n_queries, top_k, shard_sizes):
     return out
 
 
-def query_batch_sharded(snapshot, queries, score_calculator, fields_boost, top_k, comm=None):
+def query_batch_sharded(snapshot, queries, score_calculator, fields_boost, top_k, comm=None, skip=0):
     """Scores this rank's contiguous shard of `queries` on its GPU (replicated snapshot) and
     all-gathers the top-k blocks through the C ABI (ps_snapshot_query_batch_allgather_flat ->
     ncclAllGather): every rank returns the results of the whole batch.  comm=None: one rank.
-    1 <= top_k <= 1024 (PS_MAX_DEEP_TOPK)."""
+    1 <= top_k <= 1024 (PS_MAX_DEEP_TOPK).  skip > 0 (the same on every rank): every query's result page, ranks
+    [skip, skip + top_k) of the canonical order (ps_snapshot_query_batch_allgather_page_flat)."""
     from . import synth
     from .index import _boosts, _scorer_desc
     L = _lib.load()
@@ -232,9 +233,12 @@ def query_batch_sharded(snapshot, queries, score_calculator, fields_boost, top_k
     b, nb = _boosts(fields_boost)
     # stream NULL: the library scores on the snapshot's own stream, gathers on the communicator's,
     # and returns when both are done
-    _lib.check(L.ps_snapshot_query_batch_allgather_flat(snapshot._h, comm._h if comm is not None else None, C.byref(desc),
-                                                        text.ctypes.data, offsets.ctypes.data, per, b, nb, None, None,
-                                                        top_k, local.ptr, gathered.ptr, None))
+    head = (snapshot._h, comm._h if comm is not None else None, C.byref(desc), text.ctypes.data, offsets.ctypes.data, per,
+            b, nb, None, None)
+    if skip:
+        _lib.check(L.ps_snapshot_query_batch_allgather_page_flat(*head, skip, top_k, local.ptr, gathered.ptr, None))
+    else:
+        _lib.check(L.ps_snapshot_query_batch_allgather_flat(*head, top_k, local.ptr, gathered.ptr, None))
     raw = gathered.to_host()
     return unpack_blocks(raw, world, per, top_k, sizes)
 

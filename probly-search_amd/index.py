@@ -223,7 +223,11 @@ class Snapshot:
         _lib.check(self._L.ps_snapshot_get_info(self._h, C.byref(i)))
         return {k: getattr(i, k) for k, _ in i._fields_}
 
-    def query(self, query, score_calculator, tokenizer, fields_boost, top_k=0):
+    def query(self, query, score_calculator, tokenizer, fields_boost, top_k=0, skip=0):
+        """skip > 0: ranks [skip, skip + top_k) of the canonical order instead of the first top_k - a result page,
+        selected on the device (1 <= top_k <= 1024 then; see query_batch)."""
+        if skip:
+            return self.query_batch([query], score_calculator, tokenizer, fields_boost, top_k, skip=skip)[0]
         qb = query.encode("utf-8")
         desc = _scorer_desc(score_calculator)
         b, nb = _boosts(fields_boost)
@@ -244,36 +248,43 @@ class Snapshot:
             arr[i].ptr, arr[i].len = v, len(v)
         return qb, arr
 
-    def query_batch(self, queries, score_calculator, tokenizer, fields_boost, top_k=0):
-        """B independent Index::query calls in one kernel pass -> list[list[QueryResult]]."""
+    def _query_batch_c(self, desc, arr, n, b, nb, tok, skip, top_k, out, offs):
+        # skip == 0 is the existing entry point; a page goes through ps_snapshot_query_batch_page
+        try:
+            if skip:
+                _lib.check(self._L.ps_snapshot_query_batch_page(self._h, C.byref(desc), arr, n, b, nb, tok.ptr, None,
+                                                                skip, top_k, C.byref(out), C.byref(offs)))
+            else:
+                _lib.check(self._L.ps_snapshot_query_batch(self._h, C.byref(desc), arr, n, b, nb, tok.ptr, None,
+                                                           top_k, C.byref(out), C.byref(offs)))
+        except PsError as e:
+            _raise(e)
+
+    def query_batch(self, queries, score_calculator, tokenizer, fields_boost, top_k=0, skip=0):
+        """B independent Index::query calls in one kernel pass -> list[list[QueryResult]].
+        skip > 0: every query's result page, ranks [skip, skip + top_k) of the canonical order (what slicing the full
+        list gives), selected on the device however deep the page lies: 1 <= top_k <= 1024 (PS_MAX_DEEP_TOPK) and
+        skip + top_k <= 2**32 - 16."""
         qb, arr = self._pack_queries(queries)
         desc = _scorer_desc(score_calculator)
         b, nb = _boosts(fields_boost)
         tok = _Tok(tokenizer)
         out, offs = C.POINTER(_lib.Result)(), C.POINTER(C.c_size_t)()
-        try:
-            _lib.check(self._L.ps_snapshot_query_batch(self._h, C.byref(desc), arr, len(qb), b, nb, tok.ptr, None,
-                                                       top_k, C.byref(out), C.byref(offs)))
-        except PsError as e:
-            _raise(e)
+        self._query_batch_c(desc, arr, len(qb), b, nb, tok, skip, top_k, out, offs)
         res = [[QueryResult(out[j].key, out[j].score) for j in range(offs[i], offs[i + 1])] for i in range(len(qb))]
         self._L.ps_free(out)
         self._L.ps_free(offs)
         return res
 
-    def query_batch_arrays(self, queries, score_calculator, tokenizer, fields_boost, top_k):
-        """Like query_batch but returns numpy arrays (keys u64[n], scores f64[n], offsets[B+1])."""
+    def query_batch_arrays(self, queries, score_calculator, tokenizer, fields_boost, top_k, skip=0):
+        """Like query_batch (skip included) but returns numpy arrays (keys u64[n], scores f64[n], offsets[B+1])."""
         import numpy as np
         qb, arr = self._pack_queries(queries)
         desc = _scorer_desc(score_calculator)
         b, nb = _boosts(fields_boost)
         tok = _Tok(tokenizer)
         out, offs = C.POINTER(_lib.Result)(), C.POINTER(C.c_size_t)()
-        try:
-            _lib.check(self._L.ps_snapshot_query_batch(self._h, C.byref(desc), arr, len(qb), b, nb, tok.ptr, None,
-                                                       top_k, C.byref(out), C.byref(offs)))
-        except PsError as e:
-            _raise(e)
+        self._query_batch_c(desc, arr, len(qb), b, nb, tok, skip, top_k, out, offs)
         o = np.ctypeslib.as_array(offs, shape=(len(qb) + 1,)).copy()
         n = int(o[-1])
         keys, scores = np.empty(n, np.uint64), np.empty(n, np.float64)
@@ -300,15 +311,19 @@ class Snapshot:
             _raise(e)
 
     def query_batch_device_flat(self, text, offsets, score_calculator, fields_boost, top_k, d_keys, d_scores,
-                                d_counts, stream=None):
+                                d_counts, stream=None, skip=0):
         """query_batch_device with the batch as one contiguous uint8 buffer + u64 offsets[n+1]
-        (numpy arrays): no per-query marshalling on the Python side."""
+        (numpy arrays): no per-query marshalling on the Python side.  skip > 0: row i of the block holds ranks
+        [skip, skip + top_k) of query i (ps_snapshot_query_batch_device_page_flat; limits as query_batch's)."""
         desc = _scorer_desc(score_calculator)
         b, nb = _boosts(fields_boost)
+        head = (self._h, C.byref(desc), text.ctypes.data, offsets.ctypes.data, len(offsets) - 1, b, nb, None, None)
+        tail = (top_k, d_keys, d_scores, d_counts, stream if stream else None)
         try:
-            _lib.check(self._L.ps_snapshot_query_batch_device_flat(
-                self._h, C.byref(desc), text.ctypes.data, offsets.ctypes.data, len(offsets) - 1, b, nb, None, None,
-                top_k, d_keys, d_scores, d_counts, stream if stream else None))
+            if skip:
+                _lib.check(self._L.ps_snapshot_query_batch_device_page_flat(*head, skip, *tail))
+            else:
+                _lib.check(self._L.ps_snapshot_query_batch_device_flat(*head, *tail))
         except PsError as e:
             _raise(e)
 
@@ -323,15 +338,20 @@ class Snapshot:
         return hit[1], hit[2], hit[3]
 
     def query_batch_allgather_flat(self, comm, text, offsets, score_calculator, fields_boost, top_k, d_local_block,
-                                   d_all_blocks, stream=None):
+                                   d_all_blocks, stream=None, skip=0):
         """ps_snapshot_query_batch_allgather_flat: score this rank's shard into d_local_block and
         all-gather every rank's block into d_all_blocks (ncclAllGather inside the library, ordered on
-        `stream`).  comm: dist.Comm or None (one rank: no collective)."""
+        `stream`).  comm: dist.Comm or None (one rank: no collective).  skip > 0 (the same on every rank): blocks of
+        ranks [skip, skip + top_k), ps_snapshot_query_batch_allgather_page_flat."""
         desc, b, nb = self._cached_args(score_calculator, fields_boost)
+        head = (self._h, comm._h if comm is not None else None, C.byref(desc), text.ctypes.data, offsets.ctypes.data,
+                len(offsets) - 1, b, nb, None, None)
+        tail = (top_k, d_local_block, d_all_blocks, stream if stream else None)
         try:
-            _lib.check(self._L.ps_snapshot_query_batch_allgather_flat(
-                self._h, comm._h if comm is not None else None, C.byref(desc), text.ctypes.data, offsets.ctypes.data,
-                len(offsets) - 1, b, nb, None, None, top_k, d_local_block, d_all_blocks, stream if stream else None))
+            if skip:
+                _lib.check(self._L.ps_snapshot_query_batch_allgather_page_flat(*head, skip, *tail))
+            else:
+                _lib.check(self._L.ps_snapshot_query_batch_allgather_flat(*head, *tail))
         except PsError as e:
             _raise(e)
 
@@ -514,10 +534,14 @@ class Index:
         _lib.check(self._L.ps_index_vacuum(self._h))
 
     # ---- query ------------------------------------------------------------------------------
-    def query(self, query, score_calculator, tokenizer, fields_boost, top_k=0):
+    def query(self, query, score_calculator, tokenizer, fields_boost, top_k=0, skip=0):
         """Index::query(query, &mut score_calculator, tokenizer, fields_boost) (src/query.rs:21-27):
         every matching document, score desc (ties: key asc).  Runs on the GPU; the flattened
-        snapshot is rebuilt lazily after mutations."""
+        snapshot is rebuilt lazily after mutations.  skip > 0: the result page [skip, skip + top_k), see
+        Snapshot.query_batch - through a snapshot flattened for this call (the built-in scorers); a caller who
+        pages through results keeps a Snapshot and asks that."""
+        if skip:
+            return self.snapshot().query(query, score_calculator, tokenizer, fields_boost, top_k, skip=skip)
         qb = query.encode("utf-8")
         keep = None
         if getattr(score_calculator, "kind", None) == 3:  # a custom ScoreCalculator: host callbacks

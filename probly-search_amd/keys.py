@@ -105,8 +105,8 @@ class KeyedIndex:
         ks = self.keys.resolve(res)
         return [QueryResult(self._dec(k), r.score) for k, r in zip(ks, res)]
 
-    def query(self, query, score_calculator, tokenizer, fields_boost, top_k=0):
-        return self._back(self.index.query(query, score_calculator, tokenizer, fields_boost, top_k))
+    def query(self, query, score_calculator, tokenizer, fields_boost, top_k=0, skip=0):
+        return self._back(self.index.query(query, score_calculator, tokenizer, fields_boost, top_k, skip=skip))
 
     def snapshot(self, **kw):
         return KeyedSnapshot(self.index.snapshot(**kw), self)
@@ -116,9 +116,9 @@ class KeyedSnapshot:
     def __init__(self, snap, owner):
         self.snapshot, self._o = snap, owner
 
-    def query(self, query, score_calculator, tokenizer, fields_boost, top_k=0):
-        return self._o._back(self.snapshot.query(query, score_calculator, tokenizer, fields_boost, top_k))
+    def query(self, query, score_calculator, tokenizer, fields_boost, top_k=0, skip=0):
+        return self._o._back(self.snapshot.query(query, score_calculator, tokenizer, fields_boost, top_k, skip=skip))
 
-    def query_batch(self, queries, score_calculator, tokenizer, fields_boost, top_k=0):
+    def query_batch(self, queries, score_calculator, tokenizer, fields_boost, top_k=0, skip=0):
         return [self._o._back(r) for r in
-                self.snapshot.query_batch(queries, score_calculator, tokenizer, fields_boost, top_k)]
+                self.snapshot.query_batch(queries, score_calculator, tokenizer, fields_boost, top_k, skip=skip)]
