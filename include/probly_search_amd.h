@@ -147,8 +147,9 @@ int ps_device_count(void);
  * at the end between versions: a caller compiled against an older header would be written past its struct.  Compare
  * ps_abi_version() with PS_ABI_VERSION once after loading and refuse a mismatch (the Python binding does).
  * 6: ps_kernel_times.score_busy_ms (round 5), ps_comm_all_gather (round 6).
- * 7: the result-page entry points (ps_snapshot_query_batch_page, .._device_page_flat, .._allgather_page_flat). */
-#define PS_ABI_VERSION 7u
+ * 7: the result-page entry points (ps_snapshot_query_batch_page, .._device_page_flat, .._allgather_page_flat).
+ * 8: the match-count entry points (ps_snapshot_count_batch, ps_snapshot_count_batch_device_flat). */
+#define PS_ABI_VERSION 8u
 uint32_t ps_abi_version(void);
 /* Run-time options by name.  A value set here wins over the environment variable of the same name; engines read their options when
  * they are created and again at the next batch after any ps_set_option.  The list (PS_EINVAL for any other name):
@@ -382,6 +383,27 @@ ps_status ps_snapshot_query_batch_device_page_flat(ps_snapshot* snap, const ps_s
                                                    size_t n_boost, ps_tokenizer_fn tokenizer, void* user, size_t skip,
                                                    size_t top_k, void* d_keys, void* d_scores, void* d_counts,
                                                    void* hip_stream);
+
+/* Exact total match counts - the number that goes with a page, "results 21-30 of 553 210".  Index::query returns every
+ * match, so in the reference the total is results.len() (src/query.rs:97-105); totals[i] is that length for query i, i.e.
+ * what ps_snapshot_query_batch(top_k = 0) would return out_offsets[i + 1] - out_offsets[i] for, without scoring into
+ * runs, sorting or downloading them.  BM25 with every fields_boost >= 0 and zero_to_one are counted by k_count_matches -
+ * a bitset union of the query's doc-id lists under the alive bitmap, in LDS, per (query, document window) -; any other
+ * setting (a negative boost, bm25_k1 < 0, bm25_b outside [0, 1] ...) is scored like a deep top-k batch and the lengths
+ * of its runs are kept: slower, the same exact number.  Host-planned; statuses as ps_snapshot_query_batch
+ * (PS_EINVAL: null arguments, short fields_boost, host callbacks; PS_ENODEVICE; PS_EUNSUPPORTED: engine limits).
+ * totals: u64[n_queries] on the host, written whole (no need to clear it). */
+ps_status ps_snapshot_count_batch(ps_snapshot* snap, const ps_scorer_desc* scorer, const ps_str* queries, size_t n_queries,
+                                  const double* fields_boost, size_t n_boost, ps_tokenizer_fn tokenizer, void* user,
+                                  uint64_t* totals);
+/* The same total (results.len(), src/query.rs:97-105) per query into d_totals, u64[n_queries] on the snapshot's device,
+ * written whole.  text / offsets and the semantics of `hip_stream` (NULL: the snapshot's own stream, synchronous; else
+ * enqueued and ordered on it) are those of ps_snapshot_query_batch_device_flat.  A multi-GPU caller all-gathers d_totals
+ * with ps_comm_all_gather. */
+ps_status ps_snapshot_count_batch_device_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const char* text,
+                                              const uint64_t* offsets, size_t n_queries, const double* fields_boost,
+                                              size_t n_boost, ps_tokenizer_fn tokenizer, void* user, void* d_totals,
+                                              void* hip_stream);
 
 /* ---- multi-GPU: replicated corpus, query batch sharded across ranks, RCCL all-gather of top-k ----
  * Queries are independent (each Index::query owns its scores / visited maps, src/query.rs:31,37),

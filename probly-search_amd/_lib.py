@@ -18,7 +18,7 @@ class PsError(RuntimeError):
 
 PS_OK, PS_EINVAL, PS_ENOMEM, PS_EHIP, PS_EUNSUPPORTED, PS_ENODEVICE, PS_ERCCL = range(7)
 PS_COMM_ID_BYTES = 128
-PS_ABI_VERSION = 7  # include/probly_search_amd.h
+PS_ABI_VERSION = 8  # include/probly_search_amd.h
 
 
 class Str(C.Structure):
@@ -173,6 +173,10 @@ SYMBOLS = {
     "ps_snapshot_query_batch_device_page_flat": (C.c_int, [_P, C.POINTER(ScorerDesc), _P, _P, C.c_size_t,
                                                            C.POINTER(C.c_double), C.c_size_t, _P, _P, C.c_size_t,
                                                            C.c_size_t, _P, _P, _P, _P]),
+    "ps_snapshot_count_batch": (C.c_int, [_P, C.POINTER(ScorerDesc), C.POINTER(Str), C.c_size_t, C.POINTER(C.c_double),
+                                          C.c_size_t, _P, _P, _P]),
+    "ps_snapshot_count_batch_device_flat": (C.c_int, [_P, C.POINTER(ScorerDesc), _P, _P, C.c_size_t,
+                                                      C.POINTER(C.c_double), C.c_size_t, _P, _P, _P, _P]),
     "ps_snapshot_query_batch_device_planned_flat": (C.c_int, [_P, C.POINTER(ScorerDesc), _P, _P, C.c_size_t,
                                                               C.POINTER(C.c_double), C.c_size_t, C.c_size_t, _P, _P,
                                                               _P, _P]),

@@ -660,6 +660,46 @@ ps_status ps_snapshot_query_batch_device_page_flat(ps_snapshot* snap, const ps_s
                              d_scores, d_counts, hip_stream, skip);
 }
 
+// Both count entry points: host plan, Engine::run_count into h_totals (host) or d_totals (device, ordered on hip_stream).
+static ps_status run_count(ps_snapshot* snap, const ps_scorer_desc* scorer, const std::vector<std::string_view>& qs,
+                           const double* fields_boost, size_t n_boost, ps_tokenizer_fn tokenizer, void* user, void* d_totals,
+                           uint64_t* h_totals, void* hip_stream) {
+  ps_status st = check_query_args(snap, scorer, fields_boost, n_boost);
+  if (st != PS_OK) return st;
+  if (!d_totals && !h_totals) return fail(PS_EINVAL, "null argument");
+  const double t0 = wall_ms();
+  ps::Plan plan;
+  plan_batch(snap, *scorer, qs, tokenizer, user, plan);
+  const double t1 = wall_ms();
+  ps_batch_stats stats;
+  snap->engine->run_count(*scorer, fields_boost, plan, d_totals, h_totals, hip_stream, stats);
+  stats.plan_ms = t1 - t0;
+  stats.total_ms = wall_ms() - t0;
+  set_stats(snap, stats);
+  return PS_OK;
+}
+
+ps_status ps_snapshot_count_batch(ps_snapshot* snap, const ps_scorer_desc* scorer, const ps_str* queries, size_t n_queries,
+                                  const double* fields_boost, size_t n_boost, ps_tokenizer_fn tokenizer, void* user,
+                                  uint64_t* totals) {
+  return guard([&]() -> ps_status {
+    if (n_queries && !queries) return fail(PS_EINVAL, "null argument");
+    return run_count(snap, scorer, views_of(queries, n_queries), fields_boost, n_boost, tokenizer, user, nullptr, totals, nullptr);
+  });
+}
+
+ps_status ps_snapshot_count_batch_device_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const char* text,
+                                              const uint64_t* offsets, size_t n_queries, const double* fields_boost,
+                                              size_t n_boost, ps_tokenizer_fn tokenizer, void* user, void* d_totals,
+                                              void* hip_stream) {
+  return guard([&]() -> ps_status {
+    if (n_queries && (!text || !offsets)) return fail(PS_EINVAL, "null argument");
+    std::vector<std::string_view> qs(n_queries);
+    for (size_t i = 0; i < n_queries; ++i) qs[i] = std::string_view(text + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+    return run_count(snap, scorer, qs, fields_boost, n_boost, tokenizer, user, d_totals, nullptr, hip_stream);
+  });
+}
+
 ps_status ps_snapshot_query_batch_device_planned_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const char* text,
                                                       const uint64_t* offsets, size_t n_queries, const double* fields_boost,
                                                       size_t n_boost, size_t top_k, void* d_keys, void* d_scores,

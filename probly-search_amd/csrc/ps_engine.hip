@@ -182,6 +182,7 @@ struct Tuning {
   uint32_t plan_ahead_depth = 3; // PS_PLAN_AHEAD_DEPTH: batches that may be announced at a time (ps_snapshot_plan_ahead_flat)
   uint32_t score_alt = 1;        // PS_SCORE_ALT: consecutive K1d batches alternate between the scoring stream and a second one at the LOWEST stream priority (1) - a hardware queue of its own, whose kernel fills what the other's tail leaves free (two streams of one priority share a queue and serialise: 3); 0: one scoring stream; 2: everything on the low-priority stream; 4: three-way rotation normal / low / high.  Round 5, same box: C2 0.3025 -> 0.289 ms per step, C3 0.363 -> 0.312, C4 1.118 -> 0.940, C5 1.585 -> 1.213
   uint32_t device_plan = 1;      // PS_DEVICE_PLAN: flat BM25 top-k batches (built-in tokenizer) are planned by k_plan on the device
+  uint32_t count_window_log2 = 0;  // PS_COUNT_WINDOW_LOG2: documents per window of Kc k_count_matches (0: count_window_log2's rule; 8..19)
   void load();
 };
 
@@ -216,6 +217,8 @@ struct EngineImpl {
   std::mutex mu;
   // per-batch device buffers (grow-only; reuse is ordered by the stream)
   DevBuf<unsigned char> d_stage;  // plan entries + per-query arrays, uploaded once per batch (k_upload)
+  DevBuf<unsigned char> d_count;  // enqueue_count: lists | qbeg | items
+  DevBuf<unsigned long long> d_count_totals;  // ... and the totals of a call that wants them on the host
   DevBuf<uint32_t> d_cand_doc, d_out_counts, d_full_doc, d_full_cnt;
   DevBuf<double> d_cand_score, d_out_scores, d_full_score;
   DevBuf<uint64_t> d_out_keys, d_full_off;
@@ -514,7 +517,7 @@ Engine::~Engine() {
   (void)hipDeviceSynchronize();
   for (void* p : {(void*)m.d_doc, (void*)m.d_tf, (void*)m.d_fl, (void*)m.d_tfl, (void*)m.d_table, (void*)m.d_bits, (void*)m.d_alive, (void*)m.d_keys, (void*)m.d_lut, (void*)m.d_work, (void*)m.d_wstats})
     if (p) (void)hipFree(p);
-  m.d_stage.release(); m.d_cand_doc.release();
+  m.d_stage.release(); m.d_cand_doc.release(); m.d_count.release(); m.d_count_totals.release();
   m.d_out_counts.release(); m.d_full_doc.release(); m.d_full_cnt.release(); m.d_cand_score.release();
   m.d_out_scores.release(); m.d_full_score.release(); m.d_out_keys.release(); m.d_full_off.release();
   m.d_gthr.release(); m.d_rows.release(); m.d_removed_df.release();
@@ -876,6 +879,7 @@ void Tuning::load() {
     daat_z_levels = env_u32("PS_DAAT_Z_LEVELS", daat_z_levels);
     z21_field_prune = env_u32("PS_Z21_FIELD_PRUNE", z21_field_prune);
     z21_exact_numerator = env_u32("PS_Z21_EXACT_NUMERATOR", z21_exact_numerator);
+    count_window_log2 = env_u32("PS_COUNT_WINDOW_LOG2", count_window_log2);
 }
 
 namespace {
@@ -2743,8 +2747,10 @@ Plan sub_plan(const Plan& plan, size_t b, size_t e) {
 // either ring wraps (N_STAGE slots, N_KTIMER timers) the host waits for the event of the slice that last used the entry.
 // skip > 0 (a result page, any top_k in [1, PS_MAX_DEEP_TOPK]): K4w k_deep_window instead, ranks [skip, skip + top_k)
 // of every run; everything in front of the select is the same.
+// count_totals != nullptr (enqueue_count's slow route): stage 1 alone - every slice's full_cnt is widened into
+// count_totals[row] before the next slice clears it, and no select is launched.
 void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t skip, size_t top_k,
-                  void* d_keys, void* d_scores, void* d_counts, hipStream_t st) {
+                  void* d_keys, void* d_scores, void* d_counts, hipStream_t st, unsigned long long* count_totals = nullptr) {
   const Snapshot& s = *m.snap;
   const size_t B = plan.qbeg.size() - 1;
   refresh_tuning(m);
@@ -2778,12 +2784,12 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
   m.d_full_score.ensure(max_cap + 1);
   m.d_full_off.ensure(max_q + 1);
   m.d_full_cnt.ensure(max_q + 1);
-  const bool spills = max_run > (uint64_t)DEEP_CAND;  // only a run longer than the LDS candidate buffer can need the scratch
+  const bool spills = !count_totals && max_run > (uint64_t)DEEP_CAND;  // only a run longer than the LDS candidate buffer can need the scratch
   if (spills) {
     m.d_sort_doc.ensure(max_cap + 1);
     m.d_sort_score.ensure(max_cap + 1);
   }
-  allow_lds(skip ? reinterpret_cast<const void*>(&k_deep_window) : reinterpret_cast<const void*>(&k_deep_select), DEEP_LDS);
+  if (!count_totals) allow_lds(skip ? reinterpret_cast<const void*>(&k_deep_window) : reinterpret_cast<const void*>(&k_deep_select), DEEP_LDS);
   for (size_t i = 0; i + 1 < cut.size(); ++i) {
     const size_t qa = cut[i], qb = cut[i + 1], nq = qb - qa;
     const bool whole = nq == B;
@@ -2815,6 +2821,15 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
     PS_HIP(hipEventRecord(kt->b, st));
     kt->pending = true;
     m.last_kt = kt;
+    if (count_totals) {
+      hipLaunchKernelGGL(k_count_copy, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, st, m.d_full_cnt.p, count_totals + qa, (uint32_t)nq);
+      PS_HIP(hipGetLastError());
+      if (m.cur_zero_copy) {  // stage 1 reads the staging slot in place: fence it
+        PS_HIP(hipEventRecord(m.cur_stage->done, st));
+        m.cur_stage->pending = true;
+      }
+      continue;
+    }
     DeepParams dp{};
     dp.run_doc = m.d_full_doc.p;
     dp.run_score = reinterpret_cast<uint64_t*>(m.d_full_score.p);
@@ -2836,7 +2851,110 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
       m.cur_stage->pending = true;
     }
   }
-  m.wc_results += (uint64_t)B * top_k;
+  if (!count_totals) m.wc_results += (uint64_t)B * top_k;
+  PS_HIP(hipEventRecord(m.ev[0], st));
+  m.tail_stream = st;
+  m.tail_pending = true;
+}
+
+// Which way a count batch goes.  Kc k_count_matches is exact only where "the document is a result" equals "the
+// document is alive and has a posting in one of the query's lists":
+//   zero_to_one  score() returns Some for every DocumentPointer it sees (zero_to_one.rs:81) and finalize drops nothing:
+//                always, whatever the boosts (it does not read them);
+//   BM25         bm25.rs:71-92 returns Some iff the sum over the fields with tf > 0 of tfn * idf * boost * expansion_boost
+//                is > 0.  idf and expansion_boost are > 0, tfn is > 0 for k1 >= 0 and 0 <= b <= 1; with every boost > 0 each
+//                term of the sum is positive (COUNT_FAST), with boosts that are 0 or positive it is positive iff a field
+//                with a positive boost holds the term (COUNT_FAST_ZB: the kernel tests the tf planes of those fields).
+//                The products must not underflow to 0 (then the reference returns None): tfn >= ~2^-33, idf >= ~2^-34,
+//                expansion_boost >= ~2^-32 for any corpus the id space admits, so boosts from 1e-100 on are safe.
+// Anything else - a negative, tiny, infinite or NaN boost, k1 or b outside those ranges, a field whose average length
+// is not a positive finite number - is counted by the slow route: the scores themselves decide.
+enum CountRoute { COUNT_FAST, COUNT_FAST_ZB, COUNT_SLOW };
+CountRoute count_route(const Snapshot& s, const ps_scorer_desc& sc, const double* boosts, uint32_t* pos_fields) {
+  *pos_fields = 0;
+  if (sc.kind == PS_SCORER_ZERO_TO_ONE) return COUNT_FAST;
+  if (!(std::isfinite(sc.bm25_k1) && sc.bm25_k1 >= 0.0 && sc.bm25_k1 <= 1e100 && sc.bm25_b >= 0.0 && sc.bm25_b <= 1.0)) return COUNT_SLOW;
+  bool zero = false;
+  for (uint32_t x = 0; x < s.F; ++x) {
+    if (!(std::isfinite(s.avg[x]) && s.avg[x] > 0.0)) return COUNT_SLOW;
+    if (boosts[x] == 0.0) zero = true;
+    else if (std::isfinite(boosts[x]) && boosts[x] >= 1e-100) *pos_fields |= 1u << x;
+    else return COUNT_SLOW;
+  }
+  return zero ? COUNT_FAST_ZB : COUNT_FAST;
+}
+
+// Exact total match counts (src/query.rs:97-105: results.len()) of a planned batch into d_totals (u64[B], device), all
+// device work ordered on `st`.  Fast route: the items - (query, window) for every window between the query's lowest
+// first and highest last doc id, read from the host copy of the doc-id plane - are built HERE from the host plan, not
+// by a preparation kernel: the plan is on the host already (two plane reads per list), the item count sizes the grid,
+// and a kernel would have to hand that count back before the launch.  Lists, qbeg and items go up in one copy from a
+// pinned slot; totals is cleared on the stream; one launch.  Slow route: stage 1 of the deep path (enqueue_deep).
+void enqueue_count(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, unsigned long long* d_totals,
+                   hipStream_t st) {
+  const Snapshot& s = *m.snap;
+  const size_t B = plan.qbeg.size() - 1, ne = plan.entries.size();
+  refresh_tuning(m);
+  if (!B) return;
+  uint32_t pos_fields = 0;
+  const CountRoute route = count_route(s, sc, boosts, &pos_fields);
+  if (route == COUNT_SLOW) {
+    enqueue_deep(m, sc, boosts, plan, 0, 1, nullptr, nullptr, nullptr, st, d_totals);
+    return;
+  }
+  drop_ahead(m);
+  m.last_bounds_recomputed = false;
+  m.last_kt = nullptr;
+  const uint32_t w_log2 = count_window_log2(s.n_ids, B, (uint32_t)m.n_cu, m.tune.count_window_log2);
+  std::vector<CountItem> items;
+  for (size_t q = 0; q < B; ++q) {
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    for (uint32_t e = plan.qbeg[q]; e < plan.qbeg[q + 1]; ++e) {
+      const ps_plan_entry& pe = plan.entries[e];
+      if (!pe.len) continue;
+      lo = std::min(lo, s.doc[pe.post_off]);
+      hi = std::max(hi, s.doc[pe.post_off + pe.len - 1]);
+    }
+    if (lo > hi) continue;  // no posting: the total stays 0
+    for (uint32_t w = lo >> w_log2; w <= hi >> w_log2; ++w) items.push_back(CountItem{(uint32_t)q, w});
+  }
+  if (items.size() >= 0x7FFFFFF0ull) throw std::length_error("count batch too large for one launch");
+  if (m.tail_pending && m.tail_stream != st) PS_HIP(hipStreamWaitEvent(st, m.ev[0], 0));
+  m.tail_pending = false;
+  PS_HIP(hipMemsetAsync(d_totals, 0, B * 8, st));
+  if (!items.empty()) {
+    const size_t off_q = ne * sizeof(CountList), off_i = (off_q + (B + 1) * 4 + 15) & ~(size_t)15, total = off_i + items.size() * sizeof(CountItem);
+    Stage& sg = m.stage[m.next_stage];
+    m.next_stage = (m.next_stage + 1) % N_STAGE;
+    sg.ensure(total + 16);
+    CountList* hl = reinterpret_cast<CountList*>(sg.p);
+    for (size_t e = 0; e < ne; ++e) hl[e] = CountList{plan.entries[e].post_off, plan.entries[e].len, 0u};
+    memcpy(sg.p + off_q, plan.qbeg.data(), (B + 1) * 4);
+    memcpy(sg.p + off_i, items.data(), items.size() * sizeof(CountItem));
+    m.d_count.ensure(total + 16);
+    PS_HIP(hipMemcpyAsync(m.d_count.p, sg.p, total, hipMemcpyHostToDevice, st));
+    PS_HIP(hipEventRecord(sg.done, st));
+    sg.pending = true;
+    CountParams cp{};
+    cp.doc = m.d_doc;
+    cp.tf = m.d_tf;
+    cp.alive = s.any_dead ? m.d_alive : nullptr;
+    cp.lists = reinterpret_cast<const CountList*>(m.d_count.p);
+    cp.qbeg = reinterpret_cast<const uint32_t*>(m.d_count.p + off_q);
+    cp.items = reinterpret_cast<const CountItem*>(m.d_count.p + off_i);
+    cp.totals = d_totals;
+    cp.P = s.P;
+    cp.n_ids = (uint32_t)s.n_ids;
+    cp.w_log2 = w_log2;
+    cp.F = s.F;
+    cp.pos_fields = pos_fields;
+    const size_t lds = count_lds_bytes(w_log2);
+    const void* fn = route == COUNT_FAST_ZB ? reinterpret_cast<const void*>(&k_count_matches<true>) : reinterpret_cast<const void*>(&k_count_matches<false>);
+    if (lds >= 60 * 1024) PS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  // (with the static words: past 64 KiB)
+    if (route == COUNT_FAST_ZB) hipLaunchKernelGGL(k_count_matches<true>, dim3((uint32_t)items.size()), dim3(COUNT_NT), lds, st, cp);
+    else hipLaunchKernelGGL(k_count_matches<false>, dim3((uint32_t)items.size()), dim3(COUNT_NT), lds, st, cp);
+    PS_HIP(hipGetLastError());
+  }
   PS_HIP(hipEventRecord(m.ev[0], st));
   m.tail_stream = st;
   m.tail_pending = true;
@@ -3293,6 +3411,39 @@ void Engine::run_device(const ps_scorer_desc& sc, const double* boosts, const Pl
     PS_HIP(hipStreamSynchronize(st));
     read_kernel_times(m, stats);
   }
+  stats.total_ms = now_ms() - t0;
+}
+
+void Engine::run_count(const ps_scorer_desc& sc, const double* boosts, const Plan& plan, void* d_totals, uint64_t* h_totals,
+                       void* stream, ps_batch_stats& stats) {
+  EngineImpl& m = *impl_;
+  const Snapshot& s = *m.snap;
+  const size_t B = plan.qbeg.size() - 1;
+  validate(s, sc, plan);
+  std::lock_guard<std::mutex> lock(m.mu);
+  PS_HIP(hipSetDevice(m.device));
+  const double t0 = now_ms();
+  hipStream_t st = (!h_totals && stream) ? (hipStream_t)stream : m.stream;
+  if (h_totals) {
+    m.d_count_totals.ensure(B + 1);
+    m.result.ensure(B * 8 + 64);
+  }
+  unsigned long long* dt = h_totals ? m.d_count_totals.p : static_cast<unsigned long long*>(d_totals);
+  try {
+    enqueue_count(m, sc, boosts, plan, dt, st);
+    if (h_totals && B) PS_HIP(hipMemcpyAsync(m.result.p, dt, B * 8, hipMemcpyDeviceToHost, st));
+    if (h_totals || !stream) sync_stream(st);
+  } catch (...) {
+    (void)hipStreamSynchronize(st);  // nothing may still be reading the staging slot
+    throw;
+  }
+  if (h_totals && B) memcpy(h_totals, m.result.p, B * 8);
+  memset(&stats, 0, sizeof(stats));
+  stats.n_queries = B;
+  stats.n_plan_entries = plan.entries.size();
+  stats.postings_visited = plan.postings;
+  stats.algorithmic_bytes = plan.postings * 4 + (uint64_t)B * 8;  // the doc-id plane alone + the totals
+  stats.layout_bytes = stats.algorithmic_bytes;
   stats.total_ms = now_ms() - t0;
 }
 

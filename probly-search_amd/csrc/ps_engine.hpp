@@ -107,6 +107,14 @@ class Engine {
   void run_device(const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t top_k, void* d_keys,
                   void* d_scores, void* d_counts, void* stream, ps_batch_stats& stats, size_t skip = 0);
 
+  // Exact total match counts - results.len() of Index::query (src/query.rs:97-105) - without scoring into runs, sorting
+  // or downloading anything: Kc k_count_matches (ps_kernels_count.hpp) counts the union of the query's lists under the
+  // alive bitmap where that is what "matches" means (BM25 with boosts >= 0, zero_to_one); any other scorer setting
+  // takes stage 1 of the deep path and keeps its run lengths.  h_totals != nullptr: u64[B] on the host (synchronous,
+  // engine stream); else d_totals, u64[B] on the device, ordered on `stream` (nullptr = engine stream, synchronous).
+  void run_count(const ps_scorer_desc& sc, const double* boosts, const Plan& plan, void* d_totals, uint64_t* h_totals,
+                 void* stream, ps_batch_stats& stats);
+
   // SURVEY 8f N2 - device-side planner (BM25 and zero_to_one, built-in tokenizer): tokenise, term lookup in the frozen
   // trie, prefix expansion and before_each run on the GPU.  plan_device copies the plan back (tests);
   // run_device_planned scores the batch without the plan ever existing on the host.

@@ -327,6 +327,35 @@ class Snapshot:
         except PsError as e:
             _raise(e)
 
+    def count_batch(self, queries, score_calculator, fields_boost, tokenizer=None):
+        """Exact total match counts -> numpy uint64[B]: totals[i] == len(query(queries[i], ..., top_k=0)), the
+        reference's results.len() (src/query.rs:97-105), counted on the device (k_count_matches: a bitset union of the
+        query's doc-id lists) without scoring, sorting or downloading the results."""
+        import numpy as np
+        qb, arr = self._pack_queries(queries)
+        desc = _scorer_desc(score_calculator)
+        b, nb = _boosts(fields_boost)
+        tok = _Tok(tokenizer)
+        totals = np.empty(len(qb), np.uint64)
+        try:
+            _lib.check(self._L.ps_snapshot_count_batch(self._h, C.byref(desc), arr, len(qb), b, nb, tok.ptr, None,
+                                                       totals.ctypes.data))
+        except PsError as e:
+            _raise(e)
+        return totals
+
+    def count_batch_device_flat(self, text, offsets, score_calculator, fields_boost, d_totals, stream=None):
+        """count_batch into d_totals, a device pointer (int) to u64[B] on this snapshot's device; text / offsets / stream
+        as query_batch_device_flat (ps_snapshot_count_batch_device_flat)."""
+        desc = _scorer_desc(score_calculator)
+        b, nb = _boosts(fields_boost)
+        try:
+            _lib.check(self._L.ps_snapshot_count_batch_device_flat(
+                self._h, C.byref(desc), text.ctypes.data, offsets.ctypes.data, len(offsets) - 1, b, nb, None, None,
+                d_totals, stream if stream else None))
+        except PsError as e:
+            _raise(e)
+
     def _cached_args(self, score_calculator, fields_boost):
         """ctypes descriptor + boosts array for a serving loop that repeats the same scorer / boosts."""
         key = (score_calculator.kind, float(score_calculator.bm25k1), float(score_calculator.bm25b), tuple(fields_boost))

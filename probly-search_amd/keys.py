@@ -122,3 +122,6 @@ class KeyedSnapshot:
     def query_batch(self, queries, score_calculator, tokenizer, fields_boost, top_k=0, skip=0):
         return [self._o._back(r) for r in
                 self.snapshot.query_batch(queries, score_calculator, tokenizer, fields_boost, top_k, skip=skip)]
+
+    def count_batch(self, queries, score_calculator, fields_boost, tokenizer=None):
+        return self.snapshot.count_batch(queries, score_calculator, fields_boost, tokenizer)
