@@ -194,7 +194,6 @@ struct EngineImpl {
   const Snapshot* snap;
   int device;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[6] = {};
   uint32_t* d_doc = nullptr;
   uint32_t* d_tf = nullptr;
   uint32_t* d_fl = nullptr;
@@ -219,8 +218,8 @@ struct EngineImpl {
   DevBuf<unsigned char> d_stage;  // plan entries + per-query arrays, uploaded once per batch (k_upload)
   DevBuf<unsigned char> d_count;  // enqueue_count: lists | qbeg | items
   DevBuf<unsigned long long> d_count_totals;  // ... and the totals of a call that wants them on the host
-  DevBuf<uint32_t> d_cand_doc, d_out_counts, d_full_doc, d_full_cnt;
-  DevBuf<double> d_cand_score, d_out_scores, d_full_score;
+  DevBuf<uint32_t> d_cand_doc, d_full_doc, d_full_cnt;
+  DevBuf<double> d_cand_score, d_full_score;
   DevBuf<uint64_t> d_out_keys, d_full_off;
   DevBuf<unsigned long long> d_gthr;
   DevBuf<double> d_rows;  // dense per-document score rows of the batch's hot lists
@@ -364,7 +363,6 @@ struct EngineImpl {
   // batch announced that chain, not the GPU, paced C2 (streams idle between kernels; kernel timeline, round 5).
   struct Ahead { int ctx = -1; size_t B = 0, n_bytes = 0; uint64_t tune_gen = 0; };  // tune_gen: the knobs its count pass chunked the lists with
   std::deque<Ahead> aheads;
-  KTimer* last_kt_pending = nullptr;  // full-result path: the timer of the batch being enqueued
   uint64_t last_layout_bytes = 0;  // of the most recently staged batch
   uint32_t last_rows = 0, last_rows_built = 0;
   bool last_bounds_recomputed = false;
@@ -391,9 +389,8 @@ struct EngineImpl {
   bool lut_valid = false;
   double lut_k1 = 0.0, lut_b = 0.0;
   hipStream_t lut_stream = nullptr;
-  // Batches share the per-batch device buffers, so they execute one after the other.  On one
-  // stream that is stream order; a batch enqueued on another stream first waits for `tail`, the
-  // event behind the previous asynchronous batch.
+  // the event behind the previous asynchronous batch on the per-batch buffers (join_tail / publish_tail below)
+  hipEvent_t tail = nullptr;
   hipStream_t tail_stream = nullptr;
   bool tail_pending = false;
   std::map<std::pair<const void*, size_t>, size_t> occ_cache;  // (K1 instantiation, LDS bytes) -> waves per CU
@@ -438,7 +435,95 @@ struct EngineImpl {
   }
 };
 
-namespace { void forget_rows(EngineImpl& m); void ensure_bound_units(EngineImpl& m); }
+namespace {
+void forget_rows(EngineImpl& m);
+void ensure_bound_units(EngineImpl& m);
+
+// Batches share the per-batch device buffers, so they execute one after the other.  On one
+// stream that is stream order; a batch enqueued on another stream first waits for `tail`, the
+// event behind the previous asynchronous batch.  A route that uses those buffers joins before
+// its first device work on `st` and publishes behind its last; a synchronous caller, which
+// leaves nothing in flight, need not publish.
+void wait_tail(EngineImpl& m, hipStream_t st) {  // (`st` waits; the tail stays published: for streams that only read what the batches share)
+  if (m.tail_pending && m.tail_stream != st) PS_HIP(hipStreamWaitEvent(st, m.tail, 0));
+}
+void join_tail(EngineImpl& m, hipStream_t st) {
+  wait_tail(m, st);
+  m.tail_pending = false;
+}
+void publish_tail(EngineImpl& m, hipStream_t st) {
+  PS_HIP(hipEventRecord(m.tail, st));
+  m.tail_stream = st;
+  m.tail_pending = true;
+}
+
+// The next pinned staging slot of the ring (`ensure` on it waits for the batch that used it last).
+// `not_this`: a slot the batch being enqueued still needs - the one after it is claimed instead.
+Stage& claim_stage(EngineImpl& m, const Stage* not_this = nullptr) {
+  Stage* sg = &m.stage[m.next_stage];
+  m.next_stage = (m.next_stage + 1) % N_STAGE;
+  return sg == not_this ? claim_stage(m) : *sg;
+}
+// Behind the last work on `st` that reads the slot: the host does not write it again before that work is through.
+void fence_stage(Stage& sg, hipStream_t st) {
+  PS_HIP(hipEventRecord(sg.done, st));
+  sg.pending = true;
+}
+// A tiny batch's plan is read in place from its pinned slot (stage_plan: cur_zero_copy): fenced behind the last kernel that reads it.
+void fence_plan_in_place(EngineImpl& m, hipStream_t st) {
+  if (m.cur_zero_copy) fence_stage(*m.cur_stage, st);
+}
+
+// A timer of the ring for a new launch (the only place that advances the ring): whatever it still holds is harvested first.
+EngineImpl::KTimer& take_timer(EngineImpl& m, bool split) {
+  m.rebase_timers_if_stale(m.stream);
+  EngineImpl::KTimer& t = m.kt[m.next_kt];
+  m.next_kt = (m.next_kt + 1) % N_KTIMER;
+  m.harvest(t, true);
+  t.split = split;
+  return t;
+}
+// The bracket of a route whose K0 / K0b and scoring kernel run on one stream: begin_timer in front of them (null when the
+// batch is not timed), the timer's `m` to launch_score, end_timer behind the scoring kernel.  m.last_kt is the
+// batch's timer, or null.
+EngineImpl::KTimer* begin_timer(EngineImpl& m, hipStream_t st, bool timed = true) {
+  m.last_kt = nullptr;
+  if (!timed) return nullptr;
+  EngineImpl::KTimer& t = take_timer(m, false);
+  PS_HIP(hipEventRecord(t.a, st));
+  return &t;
+}
+void end_timer(EngineImpl& m, EngineImpl::KTimer* t, hipStream_t st) {
+  if (!t) return;
+  PS_HIP(hipEventRecord(t->b, st));
+  t->pending = true;
+  m.last_kt = t;
+}
+
+// The caller's result block: [B][K] keys and scores, [B] counts (device memory, or device-mapped pinned host memory).
+struct OutBlock {
+  uint64_t* keys;
+  double* scores;
+  uint32_t* counts;
+};
+OutBlock out_block(void* keys, void* scores, void* counts) {
+  return OutBlock{static_cast<uint64_t*>(keys), static_cast<double*>(scores), static_cast<uint32_t*>(counts)};
+}
+
+// A K1d batch's plan where the device reads it (uploaded by the host planner or written by the device planner), and what
+// the host knows about it.
+struct DevPlan {
+  ps_plan_entry* entries = nullptr;
+  const uint32_t* qbeg = nullptr;  // [B + 1]
+  const uint32_t* qtl = nullptr;   // [B] query_terms_len
+  size_t B = 0, ne = 0;
+  uint32_t max_qterms = 0, max_entries = 0;
+  bool multi = false;      // some query term has several expansions
+  size_t n_items = 0;      // >= the batch's work items (exact when the host knows the list lengths)
+  size_t n_items_big = 0;  // ... those of queries k_daat_small does not take (0: not known apart)
+  uint32_t max_slots = 0;  // most candidate slots of a query (0: not known; sizes K3d's workgroups)
+};
+}  // namespace
 
 int device_count() {
   int n = 0;
@@ -475,7 +560,7 @@ Engine::Engine(const Snapshot& snap, int device) : impl_(new EngineImpl()) {
     memset(m.h_fault, 0, 4 * sizeof(uint32_t));
     PS_HIP(hipHostGetDevicePointer((void**)&m.d_fault, m.h_fault, 0));
     PS_HIP(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
-    for (auto& ev : m.ev) PS_HIP(hipEventCreate(&ev));
+    PS_HIP(hipEventCreate(&m.tail));
     for (auto& sg : m.stage) PS_HIP(hipEventCreateWithFlags(&sg.done, hipEventDisableTiming));
     PS_HIP(hipEventCreateWithFlags(&m.result.done, hipEventDisableTiming));
     for (auto& t : m.kt) { PS_HIP(hipEventCreate(&t.a)); PS_HIP(hipEventCreate(&t.m)); PS_HIP(hipEventCreate(&t.b)); PS_HIP(hipEventCreate(&t.r)); }
@@ -518,8 +603,8 @@ Engine::~Engine() {
   for (void* p : {(void*)m.d_doc, (void*)m.d_tf, (void*)m.d_fl, (void*)m.d_tfl, (void*)m.d_table, (void*)m.d_bits, (void*)m.d_alive, (void*)m.d_keys, (void*)m.d_lut, (void*)m.d_work, (void*)m.d_wstats})
     if (p) (void)hipFree(p);
   m.d_stage.release(); m.d_cand_doc.release(); m.d_count.release(); m.d_count_totals.release();
-  m.d_out_counts.release(); m.d_full_doc.release(); m.d_full_cnt.release(); m.d_cand_score.release();
-  m.d_out_scores.release(); m.d_full_score.release(); m.d_out_keys.release(); m.d_full_off.release();
+  m.d_full_doc.release(); m.d_full_cnt.release(); m.d_cand_score.release();
+  m.d_full_score.release(); m.d_out_keys.release(); m.d_full_off.release();
   m.d_gthr.release(); m.d_rows.release(); m.d_removed_df.release();
   m.bounds.M.release(); m.bounds.units.release();
   if (m.bounds.m_ready) (void)hipEventDestroy(m.bounds.m_ready);
@@ -558,8 +643,7 @@ Engine::~Engine() {
   }
   if (m.result.p) (void)hipHostFree(m.result.p);
   if (m.result.done) (void)hipEventDestroy(m.result.done);
-  for (auto& ev : m.ev)
-    if (ev) (void)hipEventDestroy(ev);
+  if (m.tail) (void)hipEventDestroy(m.tail);
   for (auto& t : m.kt) {
     if (t.a) (void)hipEventDestroy(t.a);
     if (t.m) (void)hipEventDestroy(t.m);
@@ -980,8 +1064,7 @@ BatchImage lay_out_batch(EngineImpl& m, const ps_scorer_desc& sc, const Plan& pl
     img.off_zf = (img.total + 15) & ~(size_t)15;
     img.total = img.off_zf + B * m.snap->F * sizeof(double);
   }
-  Stage& sg = m.stage[m.next_stage];
-  m.next_stage = (m.next_stage + 1) % N_STAGE;
+  Stage& sg = claim_stage(m);
   sg.ensure(img.total + 16);
   img.slot = &sg;
   img.h = sg.p;
@@ -1220,12 +1303,13 @@ void check_device_fault(EngineImpl& m) {
 
 // The device-side preparation of a K1d batch (ps_prep_kernels.hpp) over a plan that already lives in
 // HBM - uploaded by the host planner or written by the device planner: bounds -> descriptors / order /
-// candidate slots -> items and dense-row flags.  `items_bound` >= the batch's item count (exact when the
-// host knows the list lengths).  Fills the K1d members of `kp`.
-void launch_prep(EngineImpl& m, EngineImpl::DaatCtx& c, const ps_scorer_desc& sc, const double* boosts, KParams& kp, ps_plan_entry* d_plan,
-                 const uint32_t* d_qbeg, size_t B, size_t ne, bool multi, size_t items_bound, bool split_kinds, size_t items_big = 0) {
+// candidate slots -> items and dense-row flags.  Fills the K1d members of `kp`.
+void launch_prep(EngineImpl& m, EngineImpl::DaatCtx& c, const ps_scorer_desc& sc, const double* boosts, KParams& kp, const DevPlan& p,
+                 bool split_kinds) {
   const Snapshot& s = *m.snap;
   hipStream_t st = m.prep_stream;
+  const size_t B = p.B, ne = p.ne, items_bound = p.n_items, items_big = split_kinds ? p.n_items_big : 0;
+  const bool multi = p.multi;
   const uint64_t rc0 = m.bounds.recomputed;
   const BoundsRef br = ensure_list_bounds(m, sc, boosts, kp, st);
   m.last_bounds_recomputed = m.bounds.recomputed != rc0;
@@ -1251,7 +1335,7 @@ void launch_prep(EngineImpl& m, EngineImpl::DaatCtx& c, const ps_scorer_desc& sc
   c.cand_cnt.ensure(items_bound + 1);
   PrepParams pp;
   memset(&pp, 0, sizeof(pp));
-  pp.plan = d_plan; pp.qbeg = d_qbeg;
+  pp.plan = p.entries; pp.qbeg = p.qbeg;
   pp.B = (uint32_t)B; pp.ne = (uint32_t)ne; pp.F = s.F; pp.multi = multi ? 1u : 0u;
   pp.chunk_min = m.tune.daat_chunk; pp.split_div = m.tune.daat_split_div;
   pp.table = m.d_table;
@@ -1354,10 +1438,9 @@ EngineImpl::DaatCtx& acquire_ctx(EngineImpl& m) {
   }
   // the batch that used this context last must be through before its buffers are written again
   if (c.busy) { PS_HIP(hipStreamWaitEvent(m.prep_stream, c.done, 0)); PS_HIP(hipStreamWaitEvent(m.plan_stream, c.done, 0)); }
-  if (m.tail_pending) {  // (a k_score / full-result batch still in flight)
-    PS_HIP(hipStreamWaitEvent(m.prep_stream, m.ev[0], 0));
-    PS_HIP(hipStreamWaitEvent(m.plan_stream, m.ev[0], 0));
-  }
+  // (a k_score / full-result batch still in flight)
+  wait_tail(m, m.prep_stream);
+  wait_tail(m, m.plan_stream);
   return c;
 }
 
@@ -1848,10 +1931,7 @@ void stage_plan(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, c
     } else {
       PS_HIP(hipMemcpyAsync(m.d_stage.p, h, up_bytes, hipMemcpyHostToDevice, st));
     }
-    if (!sync_path) {
-      PS_HIP(hipEventRecord(sg.done, st));
-      sg.pending = true;
-    }
+    if (!sync_path) fence_stage(sg, st);
     dbase = m.d_stage.p;
   }
 
@@ -2054,7 +2134,7 @@ void launch_score(EngineImpl& m, const ps_scorer_desc& sc, const Plan& plan, KPa
     if (kp.lut_rows && !(m.lut_valid && m.lut_k1 == sc.bm25_k1 && m.lut_b == sc.bm25_b && m.tune.lut_cache)) {
       for (auto& c : m.dctx)
         if (c.busy) PS_HIP(hipStreamWaitEvent(st, c.done, 0));
-      if (m.tail_pending && m.tail_stream != st) PS_HIP(hipStreamWaitEvent(st, m.ev[0], 0));
+      wait_tail(m, st);
       hipLaunchKernelGGL(k_bm25_lut, dim3(4), dim3(256), 0, st, kp, const_cast<double*>(kp.lut));
       PS_HIP(hipEventRecord(m.lut_ready, st));
       m.lut_valid = true; m.lut_k1 = sc.bm25_k1; m.lut_b = sc.bm25_b; m.lut_stream = st;
@@ -2142,15 +2222,13 @@ struct ZBatch {
   int zn = DAAT_SMALL_MAX;  // most records of a query of the batch, rounded up to an instantiation (DAAT_SMALL_MAX or Z_MAX_LISTS)
 };
 inline int z_width(uint32_t max_entries) { return max_entries <= (uint32_t)DAAT_SMALL_MAX ? DAAT_SMALL_MAX : Z_MAX_LISTS; }
-void launch_prep_z(EngineImpl& m, EngineImpl::DaatCtx& c, const ZBatch& zb, KParams& kp, ps_plan_entry* d_plan, const uint32_t* d_qbeg,
-                   size_t B, size_t ne, size_t items_bound);
+void launch_prep_z(EngineImpl& m, EngineImpl::DaatCtx& c, const ZBatch& zb, KParams& kp, const DevPlan& p);
 void launch_daat_z(EngineImpl& m, KParams& kp, hipStream_t st, int zn);
 
-void enqueue_daat(EngineImpl& m, EngineImpl::DaatCtx& c, const ps_scorer_desc& sc, const double* boosts, ps_plan_entry* d_plan,
-                  const uint32_t* d_qbeg, const uint32_t* d_qtl, size_t B, size_t ne, uint32_t max_qterms, uint32_t max_entries, bool multi,
-                  size_t n_items, uint32_t max_slots, size_t top_k, void* d_keys, void* d_scores, void* d_counts, hipStream_t caller,
-                  const ZBatch* zb = nullptr, const uint32_t* d_out_row = nullptr, size_t n_items_big = 0) {
+void enqueue_daat(EngineImpl& m, EngineImpl::DaatCtx& c, const ps_scorer_desc& sc, const double* boosts, const DevPlan& p, size_t top_k,
+                  const OutBlock& out, hipStream_t caller, const ZBatch* zb = nullptr, const uint32_t* d_out_row = nullptr) {
   const Snapshot& s = *m.snap;
+  const size_t B = p.B, n_items = p.n_items, n_items_big = p.n_items_big;
   check_device_fault(m);
   hipStream_t P = m.prep_stream, S = m.score_stream;
   if (m.tune.score_alt == 4) {  // three-way rotation: normal, low, high
@@ -2163,8 +2241,8 @@ void enqueue_daat(EngineImpl& m, EngineImpl::DaatCtx& c, const ps_scorer_desc& s
   KParams kp;
   EngineImpl::KTimer* kt = nullptr;
   try {
-    fill_common_kparams(m, sc, boosts, B, max_qterms, kp);
-    kp.plan = d_plan; kp.qbeg = d_qbeg; kp.qterms_len = d_qtl;
+    fill_common_kparams(m, sc, boosts, B, p.max_qterms, kp);
+    kp.plan = p.entries; kp.qbeg = p.qbeg; kp.qterms_len = p.qtl;
     kp.work_counter = c.work;
     const size_t n_thr = B + 2;
     bool fresh = c.gthr.ensure(n_thr, true);
@@ -2189,25 +2267,19 @@ void enqueue_daat(EngineImpl& m, EngineImpl::DaatCtx& c, const ps_scorer_desc& s
     const bool split_kinds = !zb && m.tune.daat_split && m.tune.daat_small && !m.tune.daat_persistent && n_items_big > 0 && n_items_big < n_items &&
                              n_items_big * 2 < n_items;
     kp.K = (uint32_t)top_k;  // (the preparation primes the thresholds for this K)
-    if (zb) launch_prep_z(m, c, *zb, kp, d_plan, d_qbeg, B, ne, n_items);
-    else launch_prep(m, c, sc, boosts, kp, d_plan, d_qbeg, B, ne, multi, n_items, split_kinds, split_kinds ? n_items_big : 0);
+    if (zb) launch_prep_z(m, c, *zb, kp, p);
+    else launch_prep(m, c, sc, boosts, kp, p, split_kinds);
     const size_t n_cand = n_items * top_k;
     c.cand_score.ensure(n_cand + 1);
     c.cand_doc.ensure(n_cand + 1);
     kp.cand_score = c.cand_score.p;
     kp.cand_doc = c.cand_doc.p;
-    kp.out_keys = (uint64_t*)d_keys; kp.out_scores = (double*)d_scores; kp.out_counts = (uint32_t*)d_counts;
+    kp.out_keys = out.keys; kp.out_scores = out.scores; kp.out_counts = out.counts;
     kp.out_row = d_out_row;
     // (PS_KERNEL_TIMERS=0: no HIP timing events around the launches - four stream packets less per batch between two
     // consecutive scoring kernels; ps_snapshot_kernel_breakdown then has nothing to report for these batches)
     const bool timers = m.tune.kernel_timers != 0;
-    if (timers) {
-      m.rebase_timers_if_stale(m.stream);
-      kt = &m.kt[m.next_kt];
-      m.next_kt = (m.next_kt + 1) % N_KTIMER;
-      m.harvest(*kt, true);
-      kt->split = true;
-    }
+    if (timers) kt = &take_timer(m, true);  // (a / r on the preparation stream, m / b on the scoring stream: recorded here)
     // K0b on the preparation stream too: the rows to score were listed on the device (k_prep_finish); a fixed
     // grid takes (row, tile range) units.  (It evaluates the BM25 expression itself: no table involved.)
     if (timers) PS_HIP(hipEventRecord(kt->a, P));
@@ -2242,7 +2314,7 @@ void enqueue_daat(EngineImpl& m, EngineImpl::DaatCtx& c, const ps_scorer_desc& s
       KParams kb = kp;
       kb.n_ditems = (uint32_t)n_items_big;
       kb.item_split_dev = split_at;
-      launch_daat(m, kb, multi, 0u, m.n_cu, S2);
+      launch_daat(m, kb, p.multi, 0u, m.n_cu, S2);
       PS_HIP(hipEventRecord(c.scored2, S2));
       const std::string big_name = m.score_kernel_name;
       KParams ks = kp;
@@ -2251,7 +2323,7 @@ void enqueue_daat(EngineImpl& m, EngineImpl::DaatCtx& c, const ps_scorer_desc& s
       launch_daat(m, ks, false, (uint32_t)DAAT_SMALL_MAX, m.n_cu, S);  // (the first part's longest plan is not known apart: the four-list instantiation)
       PS_HIP(hipStreamWaitEvent(S, c.scored2, 0));
       m.score_kernel_name += " + " + big_name;
-    } else launch_daat(m, kp, multi, max_entries <= (uint32_t)DAAT_SMALL_MAX ? std::max(1u, max_entries) : 0u, m.n_cu, S);
+    } else launch_daat(m, kp, p.multi, p.max_entries <= (uint32_t)DAAT_SMALL_MAX ? std::max(1u, p.max_entries) : 0u, m.n_cu, S);
 #ifdef PS_ITEM_TRACE
     {  // profiling builds: the items' start / end times of this launch -> $PS_ITEM_TRACE_FILE (last batch wins)
       PS_HIP(hipStreamSynchronize(S));
@@ -2274,7 +2346,7 @@ void enqueue_daat(EngineImpl& m, EngineImpl::DaatCtx& c, const ps_scorer_desc& s
       PS_HIP(hipEventRecord(c.entry, caller));
       PS_HIP(hipStreamWaitEvent(S, c.entry, 0));
     }
-    const uint32_t mw = max_slots ? std::min<uint32_t>(m.tune.daat_merge_waves, std::max<uint32_t>(1, (max_slots + 7) / 8)) : m.tune.daat_merge_waves;
+    const uint32_t mw = p.max_slots ? std::min<uint32_t>(m.tune.daat_merge_waves, std::max<uint32_t>(1, (p.max_slots + 7) / 8)) : m.tune.daat_merge_waves;
     hipLaunchKernelGGL(k_merge_items, dim3((uint32_t)B), dim3(WAVE * mw), 0, S, kp);
     PS_HIP(hipGetLastError());
     c.ctl_clean = true;  // k_merge_items zeroes the context's control words behind itself
@@ -2295,13 +2367,12 @@ void enqueue_daat(EngineImpl& m, EngineImpl::DaatCtx& c, const ps_scorer_desc& s
 // A host-planned K1d batch: the plan image (entries | qbeg | qterms_len) goes through a pinned slot into
 // the context's device buffer (k_upload on the context's stream), everything else as above.
 void enqueue_daat_host(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t n_items, uint32_t max_slots,
-                       size_t top_k, void* d_keys, void* d_scores, void* d_counts, hipStream_t caller, size_t n_items_big) {
+                       size_t top_k, const OutBlock& out, hipStream_t caller, size_t n_items_big) {
   EngineImpl::DaatCtx& c = acquire_ctx(m);
   hipStream_t st = m.prep_stream;
   const size_t B = plan.qbeg.size() - 1, ne = plan.entries.size();
   const size_t off_q = ne * sizeof(ps_plan_entry), off_l = off_q + (B + 1) * 4, total = (off_l + B * 4 + 15) & ~(size_t)15;
-  Stage& sg = m.stage[m.next_stage];
-  m.next_stage = (m.next_stage + 1) % N_STAGE;
+  Stage& sg = claim_stage(m);
   sg.ensure(total + 16);
   memcpy(sg.p, plan.entries.data(), ne * sizeof(ps_plan_entry));
   memcpy(sg.p + off_q, plan.qbeg.data(), (B + 1) * 4);
@@ -2311,18 +2382,21 @@ void enqueue_daat_host(EngineImpl& m, const ps_scorer_desc& sc, const double* bo
   hipLaunchKernelGGL(k_upload, dim3((uint32_t)std::max<size_t>(1, std::min<size_t>(256, (n16 + 255) / 256))), dim3(256), 0, st,
                      reinterpret_cast<const uint4*>(sg.dp), reinterpret_cast<uint4*>(c.stage.p), n16);
   PS_HIP(hipGetLastError());
-  PS_HIP(hipEventRecord(sg.done, st));
-  sg.pending = true;
-  enqueue_daat(m, c, sc, boosts, reinterpret_cast<ps_plan_entry*>(c.stage.p), reinterpret_cast<const uint32_t*>(c.stage.p + off_q),
-               reinterpret_cast<const uint32_t*>(c.stage.p + off_l), B, ne, plan.max_qterms, plan.max_entries, plan.multi_expansion, n_items, max_slots, top_k,
-               d_keys, d_scores, d_counts, caller, nullptr, nullptr, n_items_big);
+  fence_stage(sg, st);
+  DevPlan p;
+  p.entries = reinterpret_cast<ps_plan_entry*>(c.stage.p);
+  p.qbeg = reinterpret_cast<const uint32_t*>(c.stage.p + off_q);
+  p.qtl = reinterpret_cast<const uint32_t*>(c.stage.p + off_l);
+  p.B = B; p.ne = ne; p.max_qterms = plan.max_qterms; p.max_entries = plan.max_entries; p.multi = plan.multi_expansion;
+  p.n_items = n_items; p.n_items_big = n_items_big; p.max_slots = max_slots;
+  enqueue_daat(m, c, sc, boosts, p, top_k, out, caller);
 }
 
 // ---- K1dz: zero_to_one top-k batches through the K1d pipeline (ps_z21_daat.hpp) ------------------------------------
-void launch_prep_z(EngineImpl& m, EngineImpl::DaatCtx& c, const ZBatch& zb, KParams& kp, ps_plan_entry* d_plan, const uint32_t* d_qbeg,
-                   size_t B, size_t ne, size_t items_bound) {
+void launch_prep_z(EngineImpl& m, EngineImpl::DaatCtx& c, const ZBatch& zb, KParams& kp, const DevPlan& p) {
   const Snapshot& s = *m.snap;
   hipStream_t st = m.prep_stream;
+  const size_t B = p.B, ne = p.ne, items_bound = p.n_items;
   ensure_bloom(m, st);
   kp.bloom = m.d_bloom.p;
   kp.layer_bloom = m.d_layer_bloom.p;
@@ -2332,7 +2406,7 @@ void launch_prep_z(EngineImpl& m, EngineImpl::DaatCtx& c, const ZBatch& zb, KPar
   c.cand_cnt.ensure(items_bound + 1);
   ZPrepParams pp;
   memset(&pp, 0, sizeof(pp));
-  pp.plan = d_plan; pp.qbeg = d_qbeg; pp.zub = zb.d_zub; pp.table = m.d_table;
+  pp.plan = p.entries; pp.qbeg = p.qbeg; pp.zub = zb.d_zub; pp.table = m.d_table;
   pp.B = (uint32_t)B; pp.ne = (uint32_t)ne; pp.F = s.F;
   pp.chunk_min = m.tune.daat_chunk; pp.split_div = m.tune.daat_split_div;
   for (int l = 0; l < Z_LEVELS; ++l) pp.dl_tile[l] = zb.dl[l] == Z_NO_LEVEL ? 0u : zb.dl[l] >> kp.t_log2;
@@ -2455,8 +2529,8 @@ bool z_query_fits_k1dz(const Plan& plan, size_t q) {
 }
 
 // `rows` (a batch split between K1dz and the streaming kernels): the output row of each of the plan's queries.
-bool enqueue_daat_z_host(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t top_k, void* d_keys,
-                         void* d_scores, void* d_counts, hipStream_t caller, const std::vector<uint32_t>* rows = nullptr) {
+bool enqueue_daat_z_host(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t top_k, const OutBlock& out,
+                         hipStream_t caller, const std::vector<uint32_t>* rows = nullptr) {
   const Snapshot& s = *m.snap;
   const size_t B = plan.qbeg.size() - 1, ne = plan.entries.size(), F = s.F;
   if (!(m.tune.daat && m.tune.daat_z && sc.kind == PS_SCORER_ZERO_TO_ONE && B >= m.tune.daat_min_batch && ne != 0 &&
@@ -2472,8 +2546,7 @@ bool enqueue_daat_z_host(EngineImpl& m, const ps_scorer_desc& sc, const double* 
   hipStream_t st = m.prep_stream;
   const size_t off_q = ne * sizeof(ps_plan_entry), off_l = off_q + (B + 1) * 4, off_u = (off_l + B * 4 + 15) & ~(size_t)15,
                off_z = off_u + ne * 8, off_m = (off_z + ne * F * 8 + 15) & ~(size_t)15, total = (off_m + (rows ? B * 4 : 0) + 15) & ~(size_t)15;
-  Stage& sg = m.stage[m.next_stage];
-  m.next_stage = (m.next_stage + 1) % N_STAGE;
+  Stage& sg = claim_stage(m);
   sg.ensure(total + 16);
   ps_plan_entry* he = reinterpret_cast<ps_plan_entry*>(sg.p);
   double* hu = reinterpret_cast<double*>(sg.p + off_u);
@@ -2526,23 +2599,22 @@ bool enqueue_daat_z_host(EngineImpl& m, const ps_scorer_desc& sc, const double* 
   hipLaunchKernelGGL(k_upload, dim3((uint32_t)std::max<size_t>(1, std::min<size_t>(256, (n16 + 255) / 256))), dim3(256), 0, st,
                      reinterpret_cast<const uint4*>(sg.dp), reinterpret_cast<uint4*>(c.stage.p), n16);
   PS_HIP(hipGetLastError());
-  PS_HIP(hipEventRecord(sg.done, st));
-  sg.pending = true;
+  fence_stage(sg, st);
   ZBatch zb;
   zb.zn = z_width(plan.max_entries);
   zb.d_ubnum = reinterpret_cast<const double*>(c.stage.p + off_u);
   zb.d_zub = reinterpret_cast<const double*>(c.stage.p + off_z);
   z_levels(m, zb);
-  enqueue_daat(m, c, sc, boosts, reinterpret_cast<ps_plan_entry*>(c.stage.p), reinterpret_cast<const uint32_t*>(c.stage.p + off_q),
-               reinterpret_cast<const uint32_t*>(c.stage.p + off_l), B, ne, plan.max_qterms, plan.max_entries, false, n_items, max_slots, top_k,
-               d_keys, d_scores, d_counts, caller, &zb, rows ? reinterpret_cast<const uint32_t*>(c.stage.p + off_m) : nullptr);
+  DevPlan p;
+  p.entries = reinterpret_cast<ps_plan_entry*>(c.stage.p);
+  p.qbeg = reinterpret_cast<const uint32_t*>(c.stage.p + off_q);
+  p.qtl = reinterpret_cast<const uint32_t*>(c.stage.p + off_l);
+  p.B = B; p.ne = ne; p.max_qterms = plan.max_qterms; p.max_entries = plan.max_entries;
+  p.n_items = n_items; p.max_slots = max_slots;
+  enqueue_daat(m, c, sc, boosts, p, top_k, out, caller, &zb, rows ? reinterpret_cast<const uint32_t*>(c.stage.p + off_m) : nullptr);
   return true;
 }
 
-// Enqueue plan upload + K1/K2 + K3 on `st`, writing the final top-k to the given buffers (device
-// memory, or device-mapped pinned host memory).  `sync_path`: the caller waits for `st` before it
-// returns — the latency path: no staging-slot fence, and HIP timing events only for batches of
-// >= 8 queries (two extra stream packets are a visible share of a single query's round trip).
 // The queries `qs` of a plan as a plan of their own.
 Plan sub_plan_of(const Plan& plan, const std::vector<uint32_t>& qs) {
   Plan p2;
@@ -2565,13 +2637,43 @@ Plan sub_plan_of(const Plan& plan, const std::vector<uint32_t>& qs) {
   return p2;
 }
 
+// The streaming top-k of a batch whose plan `kp` already describes (stage_plan, or a device-built plan; `shape`: the
+// scalars of the plan the launch geometry needs): candidate buffers, K0 / K0b + K1 / K2 in the timer bracket, K3 k_merge
+// into `out`, all on `st`.  `sync_path`: the caller waits for `st` before it returns - the latency path, with HIP timing
+// events only for batches of >= 8 queries (two extra stream packets are a visible share of a single query's round trip).
+// The caller joins the tail in front of its staging, and fences its slots and publishes behind this.
+void score_and_merge(EngineImpl& m, const ps_scorer_desc& sc, const Plan& shape, KParams& kp, size_t top_k, const OutBlock& out,
+                     hipStream_t st, bool sync_path) {
+  static const bool time_all = env_u32("PS_TIME_ALL", 0) != 0;
+  kp.K = (uint32_t)top_k;
+  const size_t n_cand = (size_t)kp.B * kp.n_super * top_k;
+  m.d_cand_score.ensure(n_cand + 1);
+  m.d_cand_doc.ensure(n_cand + 1);
+  kp.cand_score = m.d_cand_score.p;
+  kp.cand_doc = m.d_cand_doc.p;
+  kp.out_keys = out.keys;
+  kp.out_scores = out.scores;
+  kp.out_counts = out.counts;
+  EngineImpl::KTimer* kt = begin_timer(m, st, !sync_path || kp.B >= 8 || time_all);
+  launch_score<false>(m, sc, shape, kp, m.n_cu, st, kt ? kt->m : nullptr);
+  end_timer(m, kt, st);
+  if (kp.B) {
+    // one wave per ~4 wave-wide candidate loads, at most MERGE_WAVES
+    const uint32_t mw = (uint32_t)std::min<size_t>(MERGE_WAVES, std::max<size_t>(1, ((size_t)kp.n_super * top_k + 255) / 256));
+    hipLaunchKernelGGL(k_merge, dim3(kp.B), dim3(WAVE * mw), 0, st, kp);
+    PS_HIP(hipGetLastError());
+    m.ctl_clean = true;  // k_merge zeroes the control words behind itself
+  }
+}
+
+// Enqueue plan upload + K1/K2 + K3 on `st`, writing the final top-k to the given block.  `sync_path`: the caller waits
+// for `st` before it returns, so no slot is fenced and nothing is published (score_and_merge: and small batches are not timed).
 // `rows`: the plan is one part of a split batch - query q's results go to row rows[q] of the output block.
-void enqueue_topk(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t top_k,
-                  void* d_keys, void* d_scores, void* d_counts, hipStream_t st, bool sync_path, const std::vector<uint32_t>* rows = nullptr) {
+void enqueue_topk(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t top_k, const OutBlock& out,
+                  hipStream_t st, bool sync_path, const std::vector<uint32_t>* rows = nullptr) {
   const size_t B = plan.qbeg.size() - 1;
   KParams kp;
   static const bool trace = env_u32("PS_TRACE", 0) != 0;
-  static const bool time_all = env_u32("PS_TIME_ALL", 0) != 0;
   double tt = now_ms();
   auto TT = [&](const char* what) {
     if (!trace) return;
@@ -2587,13 +2689,13 @@ void enqueue_topk(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
     size_t n_big = 0;
     const size_t n_items = count_daat_items(m, plan, &max_slots, &n_big);
     if (n_items && n_items < 0xFFFFFFF0ull) {
-      enqueue_daat_host(m, sc, boosts, plan, n_items, max_slots, top_k, d_keys, d_scores, d_counts, st, n_big);
+      enqueue_daat_host(m, sc, boosts, plan, n_items, max_slots, top_k, out, st, n_big);
       TT("k1d batch");
       return;
     }
   }
   if (sc.kind == PS_SCORER_ZERO_TO_ONE && rows == nullptr) {
-    if (enqueue_daat_z_host(m, sc, boosts, plan, top_k, d_keys, d_scores, d_counts, st)) {
+    if (enqueue_daat_z_host(m, sc, boosts, plan, top_k, out, st)) {
       TT("k1dz batch");
       return;
     }
@@ -2605,10 +2707,10 @@ void enqueue_topk(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
       for (size_t q = 0; q < B; ++q) (z_query_fits_k1dz(plan, q) ? rows_a : rows_b).push_back((uint32_t)q);
       if (rows_a.size() >= m.tune.daat_min_batch && !rows_b.empty()) {
         const Plan plan_a = sub_plan_of(plan, rows_a), plan_b = sub_plan_of(plan, rows_b);
-        if (enqueue_daat_z_host(m, sc, boosts, plan_a, top_k, d_keys, d_scores, d_counts, st, &rows_a)) {
+        if (enqueue_daat_z_host(m, sc, boosts, plan_a, top_k, out, st, &rows_a)) {
           bool second_ok = true;
           try {
-            enqueue_topk(m, sc, boosts, plan_b, top_k, d_keys, d_scores, d_counts, st, sync_path, &rows_b);
+            enqueue_topk(m, sc, boosts, plan_b, top_k, out, st, sync_path, &rows_b);
           } catch (const std::exception&) {
             // (staging the second half failed - an allocation, a length limit - with the first half already in flight: the
             // caller's block must not stay half-written, so the WHOLE batch goes through the streaming kernels below; they
@@ -2623,75 +2725,26 @@ void enqueue_topk(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
       }
     }
   }
-  if (m.tail_pending && m.tail_stream != st) PS_HIP(hipStreamWaitEvent(st, m.ev[0], 0));
-  m.tail_pending = false;
-  const bool timed = !sync_path || B >= 8 || time_all;
-  EngineImpl::KTimer* kt = nullptr;
+  join_tail(m, st);
   Stage* row_slot = nullptr;
   try {
-  stage_plan(m, sc, boosts, plan, st, kp, true, sync_path);
-  TT("stage_plan");
-  if (rows) {  // the merge kernel reads the rows from a pinned, device-mapped slot (fenced behind it below)
-    row_slot = &m.stage[m.next_stage];
-    m.next_stage = (m.next_stage + 1) % N_STAGE;
-    if (row_slot == m.cur_stage) {  // (the slot stage_plan has just filled: the next one)
-      row_slot = &m.stage[m.next_stage];
-      m.next_stage = (m.next_stage + 1) % N_STAGE;
+    stage_plan(m, sc, boosts, plan, st, kp, true, sync_path);
+    TT("stage_plan");
+    if (rows) {  // the merge kernel reads the rows from a pinned, device-mapped slot (fenced behind it below)
+      row_slot = &claim_stage(m, m.cur_stage);  // (not the slot stage_plan has just filled)
+      row_slot->ensure(B * 4 + 16);
+      memcpy(row_slot->p, rows->data(), B * 4);
+      kp.out_row = reinterpret_cast<const uint32_t*>(row_slot->dp);
     }
-    row_slot->ensure(B * 4 + 16);
-    memcpy(row_slot->p, rows->data(), B * 4);
-    kp.out_row = reinterpret_cast<const uint32_t*>(row_slot->dp);
-  }
-  kp.K = (uint32_t)top_k;
-  const size_t n_cand = (size_t)B * kp.n_super * top_k;
-  m.d_cand_score.ensure(n_cand + 1);
-  m.d_cand_doc.ensure(n_cand + 1);
-  kp.cand_score = m.d_cand_score.p;
-  kp.cand_doc = m.d_cand_doc.p;
-  TT("ctl");
-  kp.out_keys = (uint64_t*)d_keys;
-  kp.out_scores = (double*)d_scores;
-  kp.out_counts = (uint32_t*)d_counts;
-  m.last_kt = nullptr;
-  if (timed) {
-    m.rebase_timers_if_stale(m.stream);
-    kt = &m.kt[m.next_kt];
-    m.next_kt = (m.next_kt + 1) % N_KTIMER;
-    m.harvest(*kt, true);
-    kt->split = false;
-    TT("harvest");
-    PS_HIP(hipEventRecord(kt->a, st));
-  }
-  launch_score<false>(m, sc, plan, kp, m.n_cu, st, timed ? kt->m : nullptr);
+    score_and_merge(m, sc, plan, kp, top_k, out, st, sync_path);
   } catch (...) {
     forget_rows(m);
     throw;
   }
-  TT("launch");
-  if (timed) {
-    PS_HIP(hipEventRecord(kt->b, st));
-    kt->pending = true;
-    m.last_kt = kt;
-  }
-  if (B) {
-    // one wave per ~4 wave-wide candidate loads, at most MERGE_WAVES
-    const uint32_t mw = (uint32_t)std::min<size_t>(MERGE_WAVES, std::max<size_t>(1, ((size_t)kp.n_super * top_k + 255) / 256));
-    hipLaunchKernelGGL(k_merge, dim3((uint32_t)B), dim3(WAVE * mw), 0, st, kp);
-    PS_HIP(hipGetLastError());
-    m.ctl_clean = true;  // k_merge zeroes the control words behind itself
-  }
-  if (row_slot) {
-    PS_HIP(hipEventRecord(row_slot->done, st));
-    row_slot->pending = true;
-  }
-  if (m.cur_zero_copy && !sync_path) {  // the kernels read the slot in place: fence it behind them
-    PS_HIP(hipEventRecord(m.cur_stage->done, st));
-    m.cur_stage->pending = true;
-  }
+  if (row_slot) fence_stage(*row_slot, st);
   if (!sync_path) {  // a synchronous caller leaves nothing in flight
-    PS_HIP(hipEventRecord(m.ev[0], st));
-    m.tail_stream = st;
-    m.tail_pending = true;
+    fence_plan_in_place(m, st);
+    publish_tail(m, st);
   }
   TT("merge");
 }
@@ -2737,8 +2790,58 @@ Plan sub_plan(const Plan& plan, size_t b, size_t e) {
   return p2;
 }
 
-// Deep top-k (PS_MAX_DEVICE_TOPK < top_k <= PS_MAX_DEEP_TOPK): stage 1 is full-result mode's - every query's run of
-// (doc, score) behind full_off / full_cnt -, then K4s k_deep_select (ps_kernels_select.hpp) picks the first top_k of
+// ---- stage 1: every match of every query, scored into runs -------------------------------------------------------------
+// Query q's matches go to full_doc / full_score [full_off[q], full_off[q] + full_cnt[q]), unordered.  THE LAYOUT RULE: a run
+// has room for min(N, sum of the query's list lengths) matches - no query matches more -, and the runs follow each other
+// in query order.  run_caps evaluates it on the host, where the callers cut an over-budget batch into slices and size the
+// buffers; k_deep_offsets evaluates it on the device from the staged plan and is what lays the runs out, for every caller.
+// Prefix sums: cap[q + 1] - cap[q] is the room of query q's run.
+std::vector<uint64_t> run_caps(const Snapshot& s, const Plan& plan) {
+  const size_t B = plan.qbeg.size() - 1;
+  std::vector<uint64_t> cap(B + 1, 0);
+  for (size_t q = 0; q < B; ++q) {
+    uint64_t sum = 0;
+    for (uint32_t e = plan.qbeg[q]; e < plan.qbeg[q + 1]; ++e) sum += plan.entries[e].len;
+    cap[q + 1] = cap[q] + std::min<uint64_t>(sum, s.n_ids);
+  }
+  return cap;
+}
+
+// The engine's run buffers for slices of at most `max_cap` matches in at most `max_q` queries.
+void ensure_runs(EngineImpl& m, uint64_t max_cap, size_t max_q) {
+  m.d_full_doc.ensure(max_cap + 1);
+  m.d_full_score.ensure(max_cap + 1);
+  m.d_full_off.ensure(max_q + 1);
+  m.d_full_cnt.ensure(max_q + 1);
+}
+
+// Stage 1 of one slice on `st`, into the run buffers (ensure_runs; the caller has joined the tail): the plan is staged, the
+// runs are laid out and their counts cleared (k_deep_offsets), K0 / K0b + the scoring kernel run in the timer bracket, and
+// the staging slot, if the kernels read it in place, is fenced behind them.
+void score_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, hipStream_t st) {
+  KParams kp;
+  EngineImpl::KTimer* kt = nullptr;
+  try {
+    stage_plan(m, sc, boosts, plan, st, kp, false, false);
+    kp.K = 1;
+    kp.full_doc = m.d_full_doc.p;
+    kp.full_score = m.d_full_score.p;
+    kp.full_off = m.d_full_off.p;
+    kp.full_cnt = m.d_full_cnt.p;
+    hipLaunchKernelGGL(k_deep_offsets, dim3(1), dim3(DEEP_NT), 0, st, kp.plan, kp.qbeg, kp.B, kp.n_docs, m.d_full_off.p, m.d_full_cnt.p);
+    PS_HIP(hipGetLastError());
+    kt = begin_timer(m, st);
+    launch_score<true>(m, sc, plan, kp, m.n_cu, st, kt->m);
+  } catch (...) {
+    forget_rows(m);
+    throw;
+  }
+  end_timer(m, kt, st);
+  fence_plan_in_place(m, st);
+}
+
+// Deep top-k (PS_MAX_DEVICE_TOPK < top_k <= PS_MAX_DEEP_TOPK): stage 1 (score_into_runs, as in full-result mode) - every
+// query's run of (doc, score) behind full_off / full_cnt -, then K4s k_deep_select (ps_kernels_select.hpp) picks the first top_k of
 // every run into the caller's block.  All device work is ordered on `st` and no result or count comes back to the
 // host.  A batch whose runs exceed the result budget is scored in consecutive slices of queries, each writing its own
 // rows; a single query is always one slice, however long its run (the budget bounds slices, not one query's run, and
@@ -2750,21 +2853,14 @@ Plan sub_plan(const Plan& plan, size_t b, size_t e) {
 // count_totals != nullptr (enqueue_count's slow route): stage 1 alone - every slice's full_cnt is widened into
 // count_totals[row] before the next slice clears it, and no select is launched.
 void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t skip, size_t top_k,
-                  void* d_keys, void* d_scores, void* d_counts, hipStream_t st, unsigned long long* count_totals = nullptr) {
-  const Snapshot& s = *m.snap;
+                  const OutBlock& out, hipStream_t st, unsigned long long* count_totals = nullptr) {
   const size_t B = plan.qbeg.size() - 1;
   refresh_tuning(m);
   drop_ahead(m);
   m.last_bounds_recomputed = false;
   m.last_kt = nullptr;
   if (!B) return;
-  // upper bound of matches per query: min(N, sum of its list lengths) - k_deep_offsets lays the runs out by the same rule
-  std::vector<uint64_t> cap(B + 1, 0);
-  for (size_t q = 0; q < B; ++q) {
-    uint64_t sum = 0;
-    for (uint32_t e = plan.qbeg[q]; e < plan.qbeg[q + 1]; ++e) sum += plan.entries[e].len;
-    cap[q + 1] = cap[q] + std::min<uint64_t>(sum, s.n_ids);
-  }
+  const std::vector<uint64_t> cap = run_caps(*m.snap, plan);
   const uint64_t budget = (uint64_t)m.tune.full_budget_mb << 20;
   std::vector<size_t> cut{0};  // slice i = queries [cut[i], cut[i + 1])
   uint64_t max_cap = 0, max_run = 0;
@@ -2778,12 +2874,8 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
     qa = qb;
   }
   for (size_t q = 0; q < B; ++q) max_run = std::max(max_run, cap[q + 1] - cap[q]);
-  if (m.tail_pending && m.tail_stream != st) PS_HIP(hipStreamWaitEvent(st, m.ev[0], 0));
-  m.tail_pending = false;
-  m.d_full_doc.ensure(max_cap + 1);
-  m.d_full_score.ensure(max_cap + 1);
-  m.d_full_off.ensure(max_q + 1);
-  m.d_full_cnt.ensure(max_q + 1);
+  join_tail(m, st);
+  ensure_runs(m, max_cap, max_q);
   const bool spills = !count_totals && max_run > (uint64_t)DEEP_CAND;  // only a run longer than the LDS candidate buffer can need the scratch
   if (spills) {
     m.d_sort_doc.ensure(max_cap + 1);
@@ -2794,40 +2886,10 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
     const size_t qa = cut[i], qb = cut[i + 1], nq = qb - qa;
     const bool whole = nq == B;
     const Plan part = whole ? Plan() : sub_plan(plan, qa, qb);
-    const Plan& pl = whole ? plan : part;
-    KParams kp;
-    EngineImpl::KTimer* kt = nullptr;
-    try {
-      stage_plan(m, sc, boosts, pl, st, kp, false, false);
-      kp.K = 1;
-      kp.full_doc = m.d_full_doc.p;
-      kp.full_score = m.d_full_score.p;
-      kp.full_off = m.d_full_off.p;
-      kp.full_cnt = m.d_full_cnt.p;
-      hipLaunchKernelGGL(k_deep_offsets, dim3(1), dim3(DEEP_NT), 0, st, kp.plan, kp.qbeg, (uint32_t)nq, kp.n_docs, m.d_full_off.p,
-                         m.d_full_cnt.p);
-      PS_HIP(hipGetLastError());
-      m.rebase_timers_if_stale(m.stream);
-      kt = &m.kt[m.next_kt];
-      m.next_kt = (m.next_kt + 1) % N_KTIMER;
-      m.harvest(*kt, true);
-      kt->split = false;
-      PS_HIP(hipEventRecord(kt->a, st));
-      launch_score<true>(m, sc, pl, kp, m.n_cu, st, kt->m);
-    } catch (...) {
-      forget_rows(m);
-      throw;
-    }
-    PS_HIP(hipEventRecord(kt->b, st));
-    kt->pending = true;
-    m.last_kt = kt;
+    score_into_runs(m, sc, boosts, whole ? plan : part, st);
     if (count_totals) {
       hipLaunchKernelGGL(k_count_copy, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, st, m.d_full_cnt.p, count_totals + qa, (uint32_t)nq);
       PS_HIP(hipGetLastError());
-      if (m.cur_zero_copy) {  // stage 1 reads the staging slot in place: fence it
-        PS_HIP(hipEventRecord(m.cur_stage->done, st));
-        m.cur_stage->pending = true;
-      }
       continue;
     }
     DeepParams dp{};
@@ -2838,23 +2900,17 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
     dp.off = m.d_full_off.p;
     dp.cnt = m.d_full_cnt.p;
     dp.keys = m.d_keys;
-    dp.out_keys = static_cast<uint64_t*>(d_keys);
-    dp.out_scores = static_cast<double*>(d_scores);
-    dp.out_counts = static_cast<uint32_t*>(d_counts);
+    dp.out_keys = out.keys;
+    dp.out_scores = out.scores;
+    dp.out_counts = out.counts;
     dp.K = (uint32_t)top_k;
     dp.row0 = (uint32_t)qa;
     if (skip) hipLaunchKernelGGL(k_deep_window, dim3((uint32_t)nq), dim3(DEEP_NT), DEEP_LDS, st, dp, (uint32_t)skip);
     else hipLaunchKernelGGL(k_deep_select, dim3((uint32_t)nq), dim3(DEEP_NT), DEEP_LDS, st, dp);
     PS_HIP(hipGetLastError());
-    if (m.cur_zero_copy) {  // stage 1 reads the staging slot in place: fence it
-      PS_HIP(hipEventRecord(m.cur_stage->done, st));
-      m.cur_stage->pending = true;
-    }
   }
   if (!count_totals) m.wc_results += (uint64_t)B * top_k;
-  PS_HIP(hipEventRecord(m.ev[0], st));
-  m.tail_stream = st;
-  m.tail_pending = true;
+  publish_tail(m, st);
 }
 
 // Which way a count batch goes.  Kc k_count_matches is exact only where "the document is a result" equals "the
@@ -2899,7 +2955,7 @@ void enqueue_count(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts
   uint32_t pos_fields = 0;
   const CountRoute route = count_route(s, sc, boosts, &pos_fields);
   if (route == COUNT_SLOW) {
-    enqueue_deep(m, sc, boosts, plan, 0, 1, nullptr, nullptr, nullptr, st, d_totals);
+    enqueue_deep(m, sc, boosts, plan, 0, 1, OutBlock{}, st, d_totals);
     return;
   }
   drop_ahead(m);
@@ -2919,13 +2975,11 @@ void enqueue_count(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts
     for (uint32_t w = lo >> w_log2; w <= hi >> w_log2; ++w) items.push_back(CountItem{(uint32_t)q, w});
   }
   if (items.size() >= 0x7FFFFFF0ull) throw std::length_error("count batch too large for one launch");
-  if (m.tail_pending && m.tail_stream != st) PS_HIP(hipStreamWaitEvent(st, m.ev[0], 0));
-  m.tail_pending = false;
+  join_tail(m, st);
   PS_HIP(hipMemsetAsync(d_totals, 0, B * 8, st));
   if (!items.empty()) {
     const size_t off_q = ne * sizeof(CountList), off_i = (off_q + (B + 1) * 4 + 15) & ~(size_t)15, total = off_i + items.size() * sizeof(CountItem);
-    Stage& sg = m.stage[m.next_stage];
-    m.next_stage = (m.next_stage + 1) % N_STAGE;
+    Stage& sg = claim_stage(m);
     sg.ensure(total + 16);
     CountList* hl = reinterpret_cast<CountList*>(sg.p);
     for (size_t e = 0; e < ne; ++e) hl[e] = CountList{plan.entries[e].post_off, plan.entries[e].len, 0u};
@@ -2933,8 +2987,7 @@ void enqueue_count(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts
     memcpy(sg.p + off_i, items.data(), items.size() * sizeof(CountItem));
     m.d_count.ensure(total + 16);
     PS_HIP(hipMemcpyAsync(m.d_count.p, sg.p, total, hipMemcpyHostToDevice, st));
-    PS_HIP(hipEventRecord(sg.done, st));
-    sg.pending = true;
+    fence_stage(sg, st);
     CountParams cp{};
     cp.doc = m.d_doc;
     cp.tf = m.d_tf;
@@ -2955,9 +3008,7 @@ void enqueue_count(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts
     else hipLaunchKernelGGL(k_count_matches<false>, dim3((uint32_t)items.size()), dim3(COUNT_NT), lds, st, cp);
     PS_HIP(hipGetLastError());
   }
-  PS_HIP(hipEventRecord(m.ev[0], st));
-  m.tail_stream = st;
-  m.tail_pending = true;
+  publish_tail(m, st);
 }
 
 // A result page (skip > 0) is selected on the device for 1 <= top_k <= PS_MAX_DEEP_TOPK only (k_deep_window).
@@ -3143,10 +3194,8 @@ EngineImpl::DaatCtx* take_ahead(EngineImpl& m, const char* text, const uint64_t*
       m.aheads.pop_front();
       // what acquire_ctx orders for a fresh context, for whatever was enqueued since the announcement: a k_score /
       // full-result batch still in flight shares the engine's per-batch buffers and tables
-      if (m.tail_pending) {
-        PS_HIP(hipStreamWaitEvent(m.prep_stream, m.ev[0], 0));
-        PS_HIP(hipStreamWaitEvent(m.plan_stream, m.ev[0], 0));
-      }
+      wait_tail(m, m.prep_stream);
+      wait_tail(m, m.plan_stream);
       return &c;
     }
   }
@@ -3260,6 +3309,7 @@ bool Engine::run_device_planned(const ps_scorer_desc& sc, const double* boosts, 
   const double t0 = now_ms();
   m.last_bounds_recomputed = false;
   hipStream_t st = stream ? (hipStream_t)stream : m.stream;
+  const OutBlock out = out_block(d_keys, d_scores, d_counts);
   // zero_to_one: the batches K1dz takes (ps_z21_daat.hpp) are planned here; the others go back to the caller for the
   // host planner (false), before or after the count pass has classified the queries
   if (z && !(m.tune.daat && m.tune.daat_z && m.tune.device_plan && B >= m.tune.daat_min_batch && s.F <= 4 && s.n_ids > 0)) return false;
@@ -3284,6 +3334,10 @@ bool Engine::run_device_planned(const ps_scorer_desc& sc, const double* boosts, 
   if (tot.max_qterms >= 0x7FFF) throw std::length_error("more than 32766 non-empty terms in one query");
   const double t1 = now_ms();
   EngineImpl::PlanSet& ps_ = c.plan;
+  DevPlan p;  // (max_slots stays 0: the host does not know the queries' candidate slots)
+  p.entries = ps_.entries.p; p.qbeg = ps_.qbeg.p; p.qtl = ps_.qtl.p;
+  p.B = B; p.ne = tot.n_entries; p.max_qterms = tot.max_qterms; p.max_entries = tot.max_entries;
+  p.n_items = (size_t)tot.n_items;
   if (z) {
     // records into the record-sort order + their bounds (k_zplan_arrange), then K1dz as for a host-planned batch
     const size_t ne = tot.n_entries;
@@ -3301,20 +3355,18 @@ bool Engine::run_device_planned(const ps_scorer_desc& sc, const double* boosts, 
     zb.d_ubnum = ps_.z_ubnum.p;
     zb.d_zub = ps_.z_zub.p;
     z_levels(m, zb);
-    enqueue_daat(m, c, sc, boosts, ps_.entries.p, ps_.qbeg.p, ps_.qtl.p, B, ne, tot.max_qterms, tot.max_entries, false, (size_t)tot.n_items, 0u,
-                 top_k, d_keys, d_scores, d_counts, st, &zb);
+    enqueue_daat(m, c, sc, boosts, p, top_k, out, st, &zb);
   } else {
-  const bool multi = (tot.multi & PLAN_MULTI) != 0;
+  const bool multi = p.multi = (tot.multi & PLAN_MULTI) != 0;
   if (daat_eligible(m, sc, boosts, B, tot.n_entries, tot.max_entries, multi) && tot.n_items && tot.n_items < 0xFFFFFFF0ull) {
-    enqueue_daat(m, c, sc, boosts, ps_.entries.p, ps_.qbeg.p, ps_.qtl.p, B, tot.n_entries, tot.max_qterms, tot.max_entries, multi,
-                 (size_t)tot.n_items, 0u, top_k, d_keys, d_scores, d_counts, st, nullptr, nullptr, (size_t)tot.n_items_big);
+    p.n_items_big = (size_t)tot.n_items_big;
+    enqueue_daat(m, c, sc, boosts, p, top_k, out, st);
   } else {
     // the batches K1d does not take: K1 k_score / K3 k_merge from the device-built plan, in the engine's
     // single set of per-batch buffers, once nothing else is in flight
     PS_HIP(hipEventRecord(c.prepared, m.prep_stream));
     wait_daat_contexts(m, st);
-    if (m.tail_pending && m.tail_stream != st) PS_HIP(hipStreamWaitEvent(st, m.ev[0], 0));
-    m.tail_pending = false;
+    join_tail(m, st);
     PS_HIP(hipStreamWaitEvent(st, c.prepared, 0));
     Plan shape;  // the scalars the launch geometry needs; the entries stay on the device
     shape.max_entries = tot.max_entries;
@@ -3339,39 +3391,18 @@ bool Engine::run_device_planned(const ps_scorer_desc& sc, const double* boosts, 
       BatchImage img;
       img.B = B;
       choose_run_length(m, sc, shape, img, true, kp);
-      kp.K = (uint32_t)top_k;
-      const size_t n_cand = (size_t)B * kp.n_super * top_k;
-      m.d_cand_score.ensure(n_cand + 1);
-      m.d_cand_doc.ensure(n_cand + 1);
-      kp.cand_score = m.d_cand_score.p;
-      kp.cand_doc = m.d_cand_doc.p;
-      kp.out_keys = (uint64_t*)d_keys; kp.out_scores = (double*)d_scores; kp.out_counts = (uint32_t*)d_counts;
-      m.rebase_timers_if_stale(m.stream);
-      EngineImpl::KTimer* kt = &m.kt[m.next_kt];
-      m.next_kt = (m.next_kt + 1) % N_KTIMER;
-      m.harvest(*kt, true);
-      kt->split = false;
-      PS_HIP(hipEventRecord(kt->a, st));
-      m.build_slots.clear();
-      launch_score<false>(m, sc, shape, kp, m.n_cu, st, kt->m);
-      PS_HIP(hipEventRecord(kt->b, st));
-      kt->pending = true;
-      m.last_kt = kt;
-      if (B) {
-        const uint32_t mw = (uint32_t)std::min<size_t>(MERGE_WAVES, std::max<size_t>(1, ((size_t)kp.n_super * top_k + 255) / 256));
-        hipLaunchKernelGGL(k_merge, dim3((uint32_t)B), dim3(WAVE * mw), 0, st, kp);
-        PS_HIP(hipGetLastError());
-        m.ctl_clean = true;
-      }
+      m.build_slots.clear();  // (no dense rows: stage_plan, which chooses them, did not run)
+      // never the latency path: the call is asynchronous for a caller with a stream of its own, so the batch is timed and
+      // published like enqueue_topk's.  No staging slot to fence: the plan was built on the device, and cur_stage /
+      // cur_zero_copy still describe whichever host-planned batch was staged last.
+      score_and_merge(m, sc, shape, kp, top_k, out, st, false);
     } catch (...) {
       forget_rows(m);
       throw;
     }
     PS_HIP(hipEventRecord(c.done, st));  // the context's plan buffers are free again behind this batch
     c.busy = true;
-    PS_HIP(hipEventRecord(m.ev[0], st));
-    m.tail_stream = st;
-    m.tail_pending = true;
+    publish_tail(m, st);
   }
   }
   memset(&stats, 0, sizeof(stats));
@@ -3403,8 +3434,9 @@ void Engine::run_device(const ps_scorer_desc& sc, const double* boosts, const Pl
   PS_HIP(hipSetDevice(m.device));
   const double t0 = now_ms();
   hipStream_t st = stream ? (hipStream_t)stream : m.stream;
-  if (skip || top_k > PS_MAX_DEVICE_TOPK) enqueue_deep(m, sc, boosts, plan, skip, top_k, d_keys, d_scores, d_counts, st);
-  else enqueue_topk(m, sc, boosts, plan, top_k, d_keys, d_scores, d_counts, st, false);
+  const OutBlock out = out_block(d_keys, d_scores, d_counts);
+  if (skip || top_k > PS_MAX_DEVICE_TOPK) enqueue_deep(m, sc, boosts, plan, skip, top_k, out, st);
+  else enqueue_topk(m, sc, boosts, plan, top_k, out, st, false);
   memset(&stats, 0, sizeof(stats));
   fill_stats(m, stats, s, plan, (uint64_t)(plan.qbeg.size() - 1) * top_k);
   if (!stream) {
@@ -3478,9 +3510,10 @@ void Engine::run_host(const ps_scorer_desc& sc, const double* boosts, const Plan
       m.d_out_keys.ensure(res_bytes / 8 + 2);
       dres = reinterpret_cast<unsigned char*>(m.d_out_keys.p);
     }
+    const OutBlock dout = out_block(dres, dres + nb * 8, dres + nb * 16);
     try {
-      if (deep) enqueue_deep(m, sc, boosts, plan, skip, top_k, dres, dres + nb * 8, dres + nb * 16, st);
-      else enqueue_topk(m, sc, boosts, plan, top_k, dres, dres + nb * 8, dres + nb * 16, st, true);
+      if (deep) enqueue_deep(m, sc, boosts, plan, skip, top_k, dout, st);
+      else enqueue_topk(m, sc, boosts, plan, top_k, dout, st, true);
       if (!direct && res_bytes) PS_HIP(hipMemcpyAsync(m.result.p, dres, res_bytes, hipMemcpyDeviceToHost, st));
       sync_stream(st);
     } catch (...) {
@@ -3504,14 +3537,9 @@ void Engine::run_host(const ps_scorer_desc& sc, const double* boosts, const Plan
   }
 
   // ---- full-result mode: top_k == 0 (every match, like the reference) or top_k > PS_MAX_DEEP_TOPK ----------
-  // upper bound of matches per query: min(N, sum of its list lengths)
-  std::vector<uint64_t> cap(B + 1, 0);
-  for (size_t q = 0; q < B; ++q) {
-    uint64_t sum = 0;
-    for (uint32_t e = plan.qbeg[q]; e < plan.qbeg[q + 1]; ++e) sum += plan.entries[e].len;
-    cap[q + 1] = cap[q] + std::min<uint64_t>(sum, s.n_ids);
-  }
-  const uint64_t total_cap = cap[B];
+  // stage 1 (score_into_runs) of the whole batch as one slice, or - over the budget - of its halves, each sorted and
+  // downloaded on its own
+  const uint64_t total_cap = run_caps(s, plan)[B];
   const uint64_t budget = (uint64_t)m.tune.full_budget_mb << 20;
   if (B <= 1 && total_cap >= 0xFFFFFFF0ull) throw std::length_error("full-result batch too large for one pass");
   if ((total_cap * 12 > budget || total_cap >= 0xFFFFFFF0ull) && B > 1) {
@@ -3537,47 +3565,12 @@ void Engine::run_host(const ps_scorer_desc& sc, const double* boosts, const Plan
   std::lock_guard<std::mutex> lock(m.mu);
   PS_HIP(hipSetDevice(m.device));
   hipStream_t st = m.stream;
-  KParams kp;
-  if (m.tail_pending && m.tail_stream != st) PS_HIP(hipStreamWaitEvent(st, m.ev[0], 0));
-  m.tail_pending = false;
+  join_tail(m, st);
   drop_ahead(m);
-  try {
-  stage_plan(m, sc, boosts, plan, st, kp, false, false);
-  kp.K = 1;
-  m.d_full_doc.ensure(total_cap + 1);
-  m.d_full_score.ensure(total_cap + 1);
-  m.d_full_off.ensure(B + 1);
-  m.d_full_cnt.ensure(B + 1);
-  kp.full_doc = m.d_full_doc.p;
-  kp.full_score = m.d_full_score.p;
-  kp.full_off = m.d_full_off.p;
-  kp.full_cnt = m.d_full_cnt.p;
-  m.result.ensure((B + 1) * 12 + 64);
-  uint64_t* h_off = reinterpret_cast<uint64_t*>(m.result.p);
-  memcpy(h_off, cap.data(), (B + 1) * 8);
-  PS_HIP(hipMemcpyAsync(m.d_full_off.p, h_off, (B + 1) * 8, hipMemcpyHostToDevice, st));
-  PS_HIP(hipMemsetAsync(m.d_full_cnt.p, 0, (B + 1) * 4, st));
-  m.rebase_timers_if_stale(m.stream);
-  EngineImpl::KTimer& kt = m.kt[m.next_kt];
-  m.last_kt_pending = &kt;
-  m.next_kt = (m.next_kt + 1) % N_KTIMER;
-  m.harvest(kt, true);
-  kt.split = false;
-  PS_HIP(hipEventRecord(kt.a, st));
-  launch_score<true>(m, sc, plan, kp, m.n_cu, st, kt.m);
-  } catch (...) {
-    forget_rows(m);
-    throw;
-  }
-  EngineImpl::KTimer& kt = *m.last_kt_pending;
-  uint32_t* h_cnt = reinterpret_cast<uint32_t*>(m.result.p + (B + 1) * 8);
-  PS_HIP(hipEventRecord(kt.b, st));
-  kt.pending = true;
-  m.last_kt = &kt;
-  if (m.cur_zero_copy) {  // the kernel reads the staging slot in place: fence it
-    PS_HIP(hipEventRecord(m.cur_stage->done, st));
-    m.cur_stage->pending = true;
-  }
+  ensure_runs(m, total_cap, B);
+  m.result.ensure(B * 4 + 64);
+  uint32_t* h_cnt = reinterpret_cast<uint32_t*>(m.result.p);
+  score_into_runs(m, sc, boosts, plan, st);
   // K4 (query.rs:97-105, "materialise + sort"): canonical order (score desc, doc id asc == key asc)
   // of every query's run, on the device (ps_sort.hip)
   // few or huge runs: one set of device-wide sorts over all runs (needs the counts); many small runs: one segmented sort
@@ -3593,7 +3586,7 @@ void Engine::run_host(const ps_scorer_desc& sc, const double* boosts, const Plan
     m.d_sort_tmp.ensure(tb + 256);
     PS_HIP(sort_results(sb, (unsigned)total_cap, (unsigned)B, m.d_full_off.p, m.d_full_cnt.p, m.d_sort_tmp.p, tb, st));
   }
-  PS_HIP(hipMemcpyAsync(h_cnt, m.d_full_cnt.p, (B + 1) * 4, hipMemcpyDeviceToHost, st));
+  if (B) PS_HIP(hipMemcpyAsync(h_cnt, m.d_full_cnt.p, B * 4, hipMemcpyDeviceToHost, st));
   sync_stream(st);
   std::vector<uint32_t> cnt(h_cnt, h_cnt + B);
   read_kernel_times(m, stats);

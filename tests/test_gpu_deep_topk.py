@@ -137,6 +137,17 @@ def test_sliced_batch_equals_unsliced(corpus, expected, monkeypatch):
         assert_same(w, exp, (i, "unsliced"))
         assert_same(b, exp, (i, "sliced query_batch"))
         assert_same(d, exp, (i, "sliced device block"))
+    # full-result mode (every match; more than the deep path's 1024) over the same budget: the batch is halved down to
+    # single queries, each sorted and downloaded on its own
+    for name in ("bm25", "zero_to_one"):
+        sc = product_scorer(name)
+        for k in (0, 1025):
+            for i, (b, w) in enumerate(zip(snap.query_batch(queries, sc, None, BOOSTS, top_k=k),
+                                           corpus[2].query_batch(queries, sc, None, BOOSTS, top_k=k))):
+                exp = expected[name][i % len(QUERIES)]
+                exp = exp[:k] if k else exp
+                assert_same(w, exp, (name, k, i, "unsliced full"))
+                assert_same(b, exp, (name, k, i, "halved full"))
 
 
 def test_bounds(corpus, expected):
