@@ -148,8 +148,9 @@ int ps_device_count(void);
  * ps_abi_version() with PS_ABI_VERSION once after loading and refuse a mismatch (the Python binding does).
  * 6: ps_kernel_times.score_busy_ms (round 5), ps_comm_all_gather (round 6).
  * 7: the result-page entry points (ps_snapshot_query_batch_page, .._device_page_flat, .._allgather_page_flat).
- * 8: the match-count entry points (ps_snapshot_count_batch, ps_snapshot_count_batch_device_flat). */
-#define PS_ABI_VERSION 8u
+ * 8: the match-count entry points (ps_snapshot_count_batch, ps_snapshot_count_batch_device_flat).
+ * 9: ps_work_counters.run_results (thresholded stage 1 of deep top-k and result pages). */
+#define PS_ABI_VERSION 9u
 uint32_t ps_abi_version(void);
 /* Run-time options by name.  A value set here wins over the environment variable of the same name; engines read their options when
  * they are created and again at the next batch after any ps_set_option.  The list (PS_EINVAL for any other name):
@@ -543,10 +544,12 @@ typedef struct ps_work_counters {
   uint64_t rows_built;          /* K1d: dense score rows scored by K0b (k_prep_finish's choice)      */
   uint64_t rows_used;           /* K1d: dense score rows read by the batches (resident ones included) */
   uint64_t bytes_touched;       /* the formula above applied to these counts, + 12 bytes per candidate
-                                   slot written and 16 bytes per result                              */
+                                   slot written, 12 per run element (run_results) and 16 per result  */
   uint64_t z_postings_scanned;  /* K1dz (zero_to_one): the part of postings_scanned read as doc id + packed words
                                    (4 + 4F bytes instead of 4 + 8F)                                   */
   uint64_t z_lookup_hits;       /* K1dz: the part of lookup_hits that fetched packed words (4F bytes) */
+  uint64_t run_results;         /* deep top-k (top_k > 64) and result pages: (doc, score) elements stage 1 left in the
+                                   queries' runs for the select kernels, summed by those kernels from the run counts */
 } ps_work_counters;
 ps_status ps_snapshot_work_counters(ps_snapshot* snap, ps_work_counters* out, int reset);
 

@@ -18,7 +18,7 @@ class PsError(RuntimeError):
 
 PS_OK, PS_EINVAL, PS_ENOMEM, PS_EHIP, PS_EUNSUPPORTED, PS_ENODEVICE, PS_ERCCL = range(7)
 PS_COMM_ID_BYTES = 128
-PS_ABI_VERSION = 8  # include/probly_search_amd.h
+PS_ABI_VERSION = 9  # include/probly_search_amd.h
 
 
 class Str(C.Structure):
@@ -85,7 +85,7 @@ class WorkCounters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "launches", "items", "items_run", "postings_scanned", "postings_reached_lookups", "lookups_row", "lookups_cell",
         "lookups_probe", "lookup_hits", "offers", "k1_items", "k1_postings", "k1_row_slices", "results", "rows_built", "rows_used",
-        "bytes_touched", "z_postings_scanned", "z_lookup_hits")]
+        "bytes_touched", "z_postings_scanned", "z_lookup_hits", "run_results")]
 
 
 class SnapshotInfo(C.Structure):

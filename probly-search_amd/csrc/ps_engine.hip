@@ -183,6 +183,7 @@ struct Tuning {
   uint32_t score_alt = 1;        // PS_SCORE_ALT: consecutive K1d batches alternate between the scoring stream and a second one at the LOWEST stream priority (1) - a hardware queue of its own, whose kernel fills what the other's tail leaves free (two streams of one priority share a queue and serialise: 3); 0: one scoring stream; 2: everything on the low-priority stream; 4: three-way rotation normal / low / high.  Round 5, same box: C2 0.3025 -> 0.289 ms per step, C3 0.363 -> 0.312, C4 1.118 -> 0.940, C5 1.585 -> 1.213
   uint32_t device_plan = 1;      // PS_DEVICE_PLAN: flat BM25 top-k batches (built-in tokenizer) are planned by k_plan on the device
   uint32_t count_window_log2 = 0;  // PS_COUNT_WINDOW_LOG2: documents per window of Kc k_count_matches (0: count_window_log2's rule; 8..19)
+  uint32_t deep_sample_runs = 0;   // PS_DEEP_SAMPLE_RUNS: runs of a deep / paged stage 1 scored in front of k_deep_threshold (0: deep_sample_runs' rule; n: exactly n, at most n_super - 1; 0xFFFFFFFF: never threshold)
   void load();
 };
 
@@ -222,6 +223,7 @@ struct EngineImpl {
   DevBuf<double> d_cand_score, d_full_score;
   DevBuf<uint64_t> d_out_keys, d_full_off;
   DevBuf<unsigned long long> d_gthr;
+  DevBuf<unsigned long long> d_deep_thr;  // [queries of a slice] k_deep_threshold's emission thresholds (f64 bits), sized like d_full_off
   DevBuf<double> d_rows;  // dense per-document score rows of the batch's hot lists
   // K1d: per list (layer) upper bounds of the saturated term frequency, exact for the current
   // (k1, b, avg): M[l*F+x] = max tfn_x over the list's postings, J[l] = max over postings of
@@ -554,8 +556,8 @@ Engine::Engine(const Snapshot& snap, int device) : impl_(new EngineImpl()) {
     PS_HIP(hipEventCreateWithFlags(&m.lut_ready, hipEventDisableTiming));
     PS_HIP(hipEventCreateWithFlags(&m.bounds.m_ready, hipEventDisableTiming));
     for (auto& js : m.bounds.j) PS_HIP(hipEventCreateWithFlags(&js.ready, hipEventDisableTiming));
-    PS_HIP(hipMalloc((void**)&m.d_wstats, (size_t)WS_SLOTS * WS_WORDS * 8));
-    PS_HIP(hipMemset(m.d_wstats, 0, (size_t)WS_SLOTS * WS_WORDS * 8));
+    PS_HIP(hipMalloc((void**)&m.d_wstats, (size_t)WS_TOTAL_WORDS * 8));
+    PS_HIP(hipMemset(m.d_wstats, 0, (size_t)WS_TOTAL_WORDS * 8));
     PS_HIP(hipHostMalloc((void**)&m.h_fault, 4 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
     memset(m.h_fault, 0, 4 * sizeof(uint32_t));
     PS_HIP(hipHostGetDevicePointer((void**)&m.d_fault, m.h_fault, 0));
@@ -604,7 +606,7 @@ Engine::~Engine() {
     if (p) (void)hipFree(p);
   m.d_stage.release(); m.d_cand_doc.release(); m.d_count.release(); m.d_count_totals.release();
   m.d_full_doc.release(); m.d_full_cnt.release(); m.d_cand_score.release();
-  m.d_full_score.release(); m.d_out_keys.release(); m.d_full_off.release();
+  m.d_full_score.release(); m.d_out_keys.release(); m.d_full_off.release(); m.d_deep_thr.release();
   m.d_gthr.release(); m.d_rows.release(); m.d_removed_df.release();
   m.bounds.M.release(); m.bounds.units.release();
   if (m.bounds.m_ready) (void)hipEventDestroy(m.bounds.m_ready);
@@ -770,7 +772,7 @@ void Engine::work_counters(ps_work_counters& out, bool reset) {
   std::lock_guard<std::mutex> lock(m.mu);
   PS_HIP(hipSetDevice(m.device));
   PS_HIP(hipDeviceSynchronize());
-  std::vector<unsigned long long> w((size_t)WS_SLOTS * WS_WORDS);
+  std::vector<unsigned long long> w((size_t)WS_TOTAL_WORDS);
   PS_HIP(hipMemcpy(w.data(), m.d_wstats, w.size() * 8, hipMemcpyDeviceToHost));
   unsigned long long sum[WS_WORDS] = {};
   for (uint32_t sl = 0; sl < WS_SLOTS; ++sl)
@@ -792,6 +794,7 @@ void Engine::work_counters(ps_work_counters& out, bool reset) {
   out.results = m.wc_results;
   out.rows_built = sum[WS_ROWS_BUILT];
   out.rows_used = sum[WS_ROWS_USED];
+  out.run_results = w[WS_RUN_RESULTS];
   const uint64_t F = m.snap->F, pw = 4 + 4 * F;  // K1: doc id + packed words; K1d: doc id + score plane (8 bytes per field)
   // (K1dz reads the packed words where K1d reads the score plane: 4 bytes per field instead of 8)
   const uint64_t z_scanned = sum[WS_Z_SCANNED], z_hits = sum[WS_Z_HIT];
@@ -802,7 +805,7 @@ void Engine::work_counters(ps_work_counters& out, bool reset) {
   out.bytes_touched = (out.postings_scanned - z_scanned) * (4 + 8 * F) + z_scanned * pw + out.lookups_row * 8 + out.lookups_cell * 8 +
                       out.lookups_probe * 4 + (out.lookup_hits - z_hits) * 8 * F + z_hits * 4 * F + out.k1_postings * pw +
                       out.k1_row_slices * (uint64_t)m.snap->T * 8 +
-                      (m.wc_cand_slots + out.items_run * m.wc_k) * 12 + out.results * 16;
+                      (m.wc_cand_slots + out.items_run * m.wc_k + out.run_results) * 12 + out.results * 16;
   if (reset) {
     PS_HIP(hipMemset(m.d_wstats, 0, w.size() * 8));
     m.wc_launches = m.wc_items = m.wc_results = m.wc_cand_slots = 0;
@@ -964,6 +967,7 @@ void Tuning::load() {
     z21_field_prune = env_u32("PS_Z21_FIELD_PRUNE", z21_field_prune);
     z21_exact_numerator = env_u32("PS_Z21_EXACT_NUMERATOR", z21_exact_numerator);
     count_window_log2 = env_u32("PS_COUNT_WINDOW_LOG2", count_window_log2);
+    deep_sample_runs = env_u32("PS_DEEP_SAMPLE_RUNS", deep_sample_runs);
 }
 
 namespace {
@@ -1828,6 +1832,8 @@ void choose_run_length(EngineImpl& m, const ps_scorer_desc& sc, const Plan& plan
   }
   kp.S = (uint32_t)S;
   kp.n_super = (uint32_t)((s.n_tiles + S - 1) / S);
+  kp.sup_base = 0;  // (stage 1 launches: all runs, unless score_into_runs splits them)
+  kp.sup_count = kp.n_super;
   // per-wave LDS for the table slices: [entry][rb|re][S] u32; fall back to global lookups if large
   const size_t slice = (((size_t)plan.max_entries * 2 * S * 4) + 15) & ~(size_t)15;
   kp.slice_bytes = (slice <= 4096 && m.tune.slices) ? (uint32_t)slice : 0u;
@@ -2013,7 +2019,7 @@ void allow_lds(const void* fn, size_t lds) {
 
 template <int MODE, bool FULL>
 void launch_k_score(EngineImpl& m, KParams& kp, bool tags, int n_cu, hipStream_t st) {
-  const uint32_t n_items = kp.B * kp.n_super;
+  const uint32_t n_items = kp.B * (FULL ? kp.sup_count : kp.n_super);
   const uint32_t aw = MODE == MODE_Z21S ? kp.F : 1u;
   const size_t lut_b = MODE == MODE_BM25 ? (size_t)kp.lut_stride * LUT_TF * 8 : 0;
   const size_t wave_b = (size_t)kp.T * aw * 8 + (tags ? (MODE == MODE_Z21S ? (size_t)kp.T * aw * 4 : (size_t)kp.T * 2) : 0) +
@@ -2113,16 +2119,18 @@ void launch_rows(const KParams& kp, const std::vector<uint32_t>& zero_slots, hip
 }
 
 // `mid` (may be null): recorded between K0 / K0b and the scoring kernel, so the latter is timed alone
+// `again`: a further launch of the same slice over other runs (kp.sup_base / sup_count) - the scoring kernels only: the
+// slice is counted, its table and rows are built and `mid` is recorded by the first
 template <bool FULL>
 void launch_score(EngineImpl& m, const ps_scorer_desc& sc, const Plan& plan, KParams& kp, int n_cu, hipStream_t st,
-                  hipEvent_t mid) {
+                  hipEvent_t mid, bool again = false) {
   const uint32_t n_items = kp.B * kp.n_super;
   if (n_items == 0) {
     if (mid) PS_HIP(hipEventRecord(mid, st));
     return;
   }
   // host-side part of ps_work_counters (the rest is counted by the kernels)
-  m.wc_launches++;
+  if (!again) m.wc_launches++;
   if (!FULL) {
     m.wc_k = kp.K;
     m.wc_results += (uint64_t)kp.B * kp.K;
@@ -2131,7 +2139,8 @@ void launch_score(EngineImpl& m, const ps_scorer_desc& sc, const Plan& plan, KPa
   if (sc.kind == PS_SCORER_BM25) {
     // K0 runs when (k1, b) change.  The table is shared by every stream: a rebuild first waits for the K1d
     // contexts still reading it, and launches on other streams wait for the rebuild's event.
-    if (kp.lut_rows && !(m.lut_valid && m.lut_k1 == sc.bm25_k1 && m.lut_b == sc.bm25_b && m.tune.lut_cache)) {
+    if (again) {
+    } else if (kp.lut_rows && !(m.lut_valid && m.lut_k1 == sc.bm25_k1 && m.lut_b == sc.bm25_b && m.tune.lut_cache)) {
       for (auto& c : m.dctx)
         if (c.busy) PS_HIP(hipStreamWaitEvent(st, c.done, 0));
       wait_tail(m, st);
@@ -2141,11 +2150,11 @@ void launch_score(EngineImpl& m, const ps_scorer_desc& sc, const Plan& plan, KPa
     } else if (kp.lut_rows && m.lut_stream != st) {
       PS_HIP(hipStreamWaitEvent(st, m.lut_ready, 0));
     }
-    launch_rows(kp, m.build_slots, st);
+    if (!again) launch_rows(kp, m.build_slots, st);
     if (mid) PS_HIP(hipEventRecord(mid, st));
     launch_k_score<MODE_BM25, FULL>(m, kp, plan.multi_expansion, n_cu, st);
   } else {
-    launch_rows(kp, m.build_slots, st);
+    if (!again) launch_rows(kp, m.build_slots, st);
     if (mid) PS_HIP(hipEventRecord(mid, st));
     if (kp.n_simple) launch_k_score<MODE_Z21S, FULL>(m, kp, kp.z_masked != 0, n_cu, st);
     if (kp.n_general) {
@@ -2167,7 +2176,7 @@ void launch_score(EngineImpl& m, const ps_scorer_desc& sc, const Plan& plan, KPa
         const void* fn = FULL ? reinterpret_cast<const void*>(&k_z21<true>) : reinterpret_cast<const void*>(&k_z21<false>);
         allow_lds(fn, (size_t)zt * per_doc);
       }
-      hipLaunchKernelGGL((k_z21<FULL>), dim3(kp.n_general * kp.n_super), dim3(WAVE), (size_t)zt * per_doc, st, kp);
+      hipLaunchKernelGGL((k_z21<FULL>), dim3(kp.n_general * (FULL ? kp.sup_count : kp.n_super)), dim3(WAVE), (size_t)zt * per_doc, st, kp);
     }
   }
   PS_HIP(hipGetLastError());
@@ -2813,12 +2822,39 @@ void ensure_runs(EngineImpl& m, uint64_t max_cap, size_t max_q) {
   m.d_full_score.ensure(max_cap + 1);
   m.d_full_off.ensure(max_q + 1);
   m.d_full_cnt.ensure(max_q + 1);
+  m.d_deep_thr.ensure(max_q + 1);
+}
+
+// THE SAMPLE RULE of a thresholded stage 1: how many of the slice's n_super runs are scored in
+// front of k_deep_threshold; 0 = one unthresholded launch.  A query of M matches leaves about f M + hi / f elements
+// when the fraction f of the runs is the sample, least at f = sqrt(hi / M): M is taken as the median room of the
+// slice's runs that are worth thresholding at all (more than 4 hi), and the sample is never more than half of the runs.
+uint32_t deep_sample_runs(const EngineImpl& m, const Plan& plan, uint32_t n_super, uint32_t hi) {
+  const uint32_t knob = m.tune.deep_sample_runs;
+  if (knob == 0xFFFFFFFFu || n_super < 2) return 0;
+  if (knob) return std::min(knob, n_super - 1);
+  const std::vector<uint64_t> cap = run_caps(*m.snap, plan);
+  std::vector<uint64_t> rooms;
+  for (size_t q = 0; q + 1 < cap.size(); ++q)
+    if (cap[q + 1] - cap[q] > 4ull * hi) rooms.push_back(cap[q + 1] - cap[q]);
+  if (rooms.empty()) return 0;
+  std::nth_element(rooms.begin(), rooms.begin() + rooms.size() / 2, rooms.end());
+  const double f = std::sqrt((double)hi / (double)rooms[rooms.size() / 2]);
+  return std::min(std::max((uint32_t)std::ceil(f * n_super), 1u), n_super / 2);
 }
 
 // Stage 1 of one slice on `st`, into the run buffers (ensure_runs; the caller has joined the tail): the plan is staged, the
 // runs are laid out and their counts cleared (k_deep_offsets), K0 / K0b + the scoring kernel run in the timer bracket, and
 // the staging slot, if the kernels read it in place, is fenced behind them.
-void score_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, hipStream_t st) {
+// hi = 0: every match is emitted (full-result mode, the slow count route).  hi > 0 (deep top-k and result pages: only
+// ranks [0, hi) are wanted): the scoring kernels run twice - over the first s0 runs (deep_sample_runs), emitting
+// everything, and over the rest, emitting what scores >= thr[q] - with k_deep_threshold between them: thr[q] is the
+// hi-th best score of query q's sample, a lower bound of its final hi-th best, so no document of ranks [0, hi) is
+// dropped, equal scores are kept for the select's doc-id levels to order, and a run that was filtered (thr > 0) holds
+// at least hi elements.  That needs every score of the route to be a non-NaN value >= +0.0: zero_to_one, or BM25 under
+// bm25_params_sane; other parameters keep the single launch.
+void score_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, hipStream_t st,
+                     uint32_t hi = 0) {
   KParams kp;
   EngineImpl::KTimer* kt = nullptr;
   try {
@@ -2830,8 +2866,21 @@ void score_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boos
     kp.full_cnt = m.d_full_cnt.p;
     hipLaunchKernelGGL(k_deep_offsets, dim3(1), dim3(DEEP_NT), 0, st, kp.plan, kp.qbeg, kp.B, kp.n_docs, m.d_full_off.p, m.d_full_cnt.p);
     PS_HIP(hipGetLastError());
+    const bool ordered_bits = sc.kind == PS_SCORER_ZERO_TO_ONE || bm25_params_sane(*m.snap, sc, boosts);
+    const uint32_t s0 = hi && ordered_bits ? deep_sample_runs(m, plan, kp.n_super, hi) : 0u;
     kt = begin_timer(m, st);
+    if (s0) kp.sup_count = s0;
     launch_score<true>(m, sc, plan, kp, m.n_cu, st, kt->m);
+    if (s0) {
+      allow_lds(reinterpret_cast<const void*>(&k_deep_threshold), THR_LDS);
+      hipLaunchKernelGGL(k_deep_threshold, dim3(kp.B), dim3(THR_NT), THR_LDS, st, reinterpret_cast<const uint64_t*>(kp.full_score),
+                         kp.full_off, kp.full_cnt, hi, m.d_deep_thr.p);
+      PS_HIP(hipMemsetAsync(m.d_work, 0, 256, st));  // the persistent waves' item counter, as between batches
+      kp.sup_base = s0;
+      kp.sup_count = kp.n_super - s0;
+      kp.emit_thr = m.d_deep_thr.p;
+      launch_score<true>(m, sc, plan, kp, m.n_cu, st, nullptr, true);
+    }
   } catch (...) {
     forget_rows(m);
     throw;
@@ -2886,7 +2935,8 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
     const size_t qa = cut[i], qb = cut[i + 1], nq = qb - qa;
     const bool whole = nq == B;
     const Plan part = whole ? Plan() : sub_plan(plan, qa, qb);
-    score_into_runs(m, sc, boosts, whole ? plan : part, st);
+    // only ranks [0, skip + top_k) are wanted: stage 1 may drop what cannot reach them (the count route wants every match)
+    score_into_runs(m, sc, boosts, whole ? plan : part, st, count_totals ? 0u : (uint32_t)(skip + top_k));  // (check_page: below 2^32)
     if (count_totals) {
       hipLaunchKernelGGL(k_count_copy, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, st, m.d_full_cnt.p, count_totals + qa, (uint32_t)nq);
       PS_HIP(hipGetLastError());
@@ -2905,6 +2955,7 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
     dp.out_counts = out.counts;
     dp.K = (uint32_t)top_k;
     dp.row0 = (uint32_t)qa;
+    dp.run_results = m.d_wstats + WS_RUN_RESULTS;
     if (skip) hipLaunchKernelGGL(k_deep_window, dim3((uint32_t)nq), dim3(DEEP_NT), DEEP_LDS, st, dp, (uint32_t)skip);
     else hipLaunchKernelGGL(k_deep_select, dim3((uint32_t)nq), dim3(DEEP_NT), DEEP_LDS, st, dp);
     PS_HIP(hipGetLastError());

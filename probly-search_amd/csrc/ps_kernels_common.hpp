@@ -123,6 +123,7 @@ struct KParams {
   const uint32_t* gen_queries; // zero_to_one: the n_general queries k_z21 has to run
   const uint32_t* qflags;      // zero_to_one: bit 0 = "simple" query (k_score<MODE_Z21S> owns it)
   uint32_t slice_bytes;        // per-wave LDS for the table slices (0 = look ranges up in global memory)
+  uint32_t sup_base;           // full-result mode: a launch covers the runs [sup_base, sup_base + sup_count)
   const uint32_t* zorder;      // zero_to_one: per query, entry indices sorted by (score desc, plan order)
   const double* zfub;          // zero_to_one: [B][F] upper bound of any document's pool of field x for query q (null: none)
   uint64_t P;
@@ -140,6 +141,7 @@ struct KParams {
   uint32_t n_rows;
   uint32_t row_mode;    // MODE_BM25 | MODE_Z21S: what k_dense_rows evaluates
   uint32_t row_planes;  // 1 (BM25 score) | F (zero_to_one: one contribution plane per field)
+  uint32_t sup_count;   // (see sup_base)
   uint64_t layout_bytes;         // host-side bookkeeping: bytes of the layout actually streamed
   uint32_t z_masked;             // host-side: some simple query needs the consumed-query-term masks
   uint32_t n_simple, n_general;  // host-side bookkeeping (zero_to_one query classes in this batch)
@@ -188,6 +190,9 @@ struct KParams {
   double* out_scores;
   uint32_t* out_counts;
   const uint32_t* out_row;   // [B] the output row of query q; nullptr: q itself (set when a batch is split between two scoring kernels)
+  // full-result mode, stage 1's second launch for deep top-k and result pages: a document is only emitted when its score is
+  // >= the query's threshold (f64 bits; k_deep_threshold)
+  const unsigned long long* emit_thr;  // [B], null = no filter
 };
 
 // ------------------------------------------------------------------------------------------
@@ -199,6 +204,8 @@ struct KParams {
 #define PS_WORK_COUNTERS 1   // 0: a build without the counters (A/B of their cost only)
 #endif
 constexpr uint32_t WS_SLOTS = 64, WS_WORDS = 16;  // one 128-byte line per slot
+constexpr uint32_t WS_RUN_RESULTS = WS_SLOTS * WS_WORDS;  // behind the slots, a line of its own: elements stage 1 left in the runs the select kernels read
+constexpr uint32_t WS_TOTAL_WORDS = WS_RUN_RESULTS + WS_WORDS;
 enum { WS_ITEMS_RUN = 0, WS_SCANNED, WS_REACHED, WS_ROW, WS_CELL, WS_PROBE, WS_HIT, WS_OFFER, WS_K1_ITEMS, WS_K1_POSTINGS,
        WS_K1_ROWSLICES, WS_ROWS_BUILT, WS_ROWS_USED, WS_ITEMS, WS_Z_SCANNED, WS_Z_HIT };  // (WS_Z_*: K1dz reads packed words, 4 bytes per field)
 struct WorkStats {  // K1d, per item
@@ -278,8 +285,18 @@ __device__ __forceinline__ void topk_offer(TopK& tk, const uint32_t K, const int
   }
 }
 
-// Full-result mode: append this wave's present documents to the query's output run.
-__device__ __forceinline__ void full_emit(const KParams& p, uint32_t q, int lane, bool has, double v, uint32_t d) {
+// The emission filter of query q, read once per item (wave-uniform): `on` = the launch has thresholds.
+struct EmitFilter { bool on; double thr; };
+struct NoEmitFilter {};  // (what the top-k instantiations carry instead: no state at all)
+__device__ __forceinline__ EmitFilter emit_filter(const KParams& p, const uint32_t q) {
+  const bool on = p.emit_thr != nullptr;
+  return EmitFilter{on, on ? __longlong_as_double((long long)p.emit_thr[q]) : 0.0};
+}
+
+// Full-result mode: append this wave's present documents to the query's output run (`filt`: those scoring >= thr).
+__device__ __forceinline__ void full_emit(const KParams& p, uint32_t q, int lane, bool has, double v, uint32_t d,
+                                          const EmitFilter ef) {
+  if (ef.on) has = has && v >= ef.thr;
   unsigned long long m = __ballot(has);
   if (m == 0) return;
   uint32_t base = 0;
@@ -298,10 +315,14 @@ __device__ __forceinline__ void full_emit(const KParams& p, uint32_t q, int lane
 // (~170 ns each measured: 2.7 ms for the 24 x 15 k reservations of a C2 full-result batch when every 64 documents
 // made their own).
 template <int N>
-__device__ __forceinline__ void full_emit_group(const KParams& p, uint32_t q, int lane, const bool (&has)[N],
-                                                const double (&v)[N], const uint32_t (&d)[N]) {
+__device__ __forceinline__ void full_emit_group(const KParams& p, uint32_t q, int lane, bool (&has)[N],
+                                                const double (&v)[N], const uint32_t (&d)[N], const EmitFilter ef) {
   unsigned long long m[N];
   uint32_t tot = 0;
+  if (ef.on) {  // (wave-uniform)
+#pragma unroll
+    for (int i = 0; i < N; ++i) has[i] = has[i] && v[i] >= ef.thr;
+  }
 #pragma unroll
   for (int i = 0; i < N; ++i) {
     m[i] = __ballot(has[i]);

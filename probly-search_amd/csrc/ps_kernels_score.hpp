@@ -552,7 +552,7 @@ __global__ __launch_bounds__(WAVE * WGW) void k_score(const KParams p) {
       for (uint32_t i = lane; i < T; i += WAVE) tag[i] = 0xFFFFu;
   }
   uint32_t tagbase = 0;
-  const uint32_t n_items = p.B * p.n_super;
+  const uint32_t n_items = p.B * (FULL ? p.sup_count : p.n_super);  // (FULL: this launch's runs only)
   // A grid that covers every item with its own wave (a single query: ~1000 waves that would
   // otherwise all queue on one L2 word before doing anything) assigns them by index; otherwise
   // items come from the shared counter.
@@ -570,9 +570,11 @@ __global__ __launch_bounds__(WAVE * WGW) void k_score(const KParams p) {
   }
   if (item >= n_items) break;
   const uint32_t q = p.qorder[item % p.B];
-  const uint32_t sup = item / p.B;
+  const uint32_t sup = FULL ? p.sup_base + item / p.B : item / p.B;
   const uint32_t e0 = p.qbeg[q], e1 = p.qbeg[q + 1];
   const uint32_t ne = e1 - e0;
+  std::conditional_t<FULL, EmitFilter, NoEmitFilter> ef;
+  if constexpr (FULL) ef = emit_filter(p, q);
   const bool mine = MODE == MODE_BM25 || (p.qflags[q] & 1u);  // Z21S: only "simple" queries
   if (MODE == MODE_Z21S && !mine) continue;                   // k_z21 owns this query's candidate slots
   const uint32_t qtl = MODE == MODE_Z21S ? p.qterms_len[q] : 0u;
@@ -746,7 +748,7 @@ __global__ __launch_bounds__(WAVE * WGW) void k_score(const KParams p) {
               }
             }
           }
-          if (FULL) full_emit_group(p, q, lane, fh, fv, fd);
+          if constexpr (FULL) full_emit_group(p, q, lane, fh, fv, fd, ef);
         };
         uint32_t c = 0;
         if (!TAGS && fuse_row != 0xFFFFFFFFu) {
@@ -831,7 +833,7 @@ __global__ __launch_bounds__(WAVE * WGW) void k_score(const KParams p) {
                 }
               }
             }
-            if (FULL) full_emit_group(p, q, lane, fh, fv, fd);
+            if constexpr (FULL) full_emit_group(p, q, lane, fh, fv, fd, ef);
           }
         };
         const uint32_t fm2 = fmask & 3u;  // wave-uniform
@@ -900,13 +902,15 @@ __global__ __launch_bounds__(WAVE) void k_z21(const KParams p) {
   const int lane = threadIdx.x;
   // grid = n_general x n_super: only the queries the simple path could not take
   const uint32_t q = p.gen_queries[blockIdx.x % p.n_general];
-  const uint32_t sup = blockIdx.x / p.n_general;
+  const uint32_t sup = (FULL ? p.sup_base : 0u) + blockIdx.x / p.n_general;  // (FULL: the grid covers sup_count runs)
   const uint32_t item = sup * p.B + q;  // candidate slot, as k_merge expects it
   const uint32_t e0 = p.qbeg[q], e1 = p.qbeg[q + 1];
 
   TopK tk;
   tk.s = -1.0; tk.d = 0xFFFFFFFFu; tk.n = 0; tk.thr_s = 0.0; tk.thr_d = 0;
   uint32_t ws_post = 0;  // work counter: postings streamed (exact planes: 4 + 8F bytes each here)
+  std::conditional_t<FULL, EmitFilter, NoEmitFilter> ef;
+  if constexpr (FULL) ef = emit_filter(p, q);
 
   if (e0 != e1) {
     for (uint32_t i = lane; i < ZT * stride; i += WAVE) rec[i] = 0;
@@ -979,7 +983,7 @@ __global__ __launch_bounds__(WAVE) void k_z21(const KParams p) {
             for (uint32_t w = 0; w < stride; ++w) rec[local * stride + w] = 0;
           const uint32_t d = tile_base + local;
           has = has && (d < p.n_docs) && doc_alive(p, d);
-          if (FULL) full_emit(p, q, lane, has, best, d);
+          if constexpr (FULL) full_emit(p, q, lane, has, best, d, ef);
           else topk_offer(tk, p.K, lane, has, best, d);
         }
       }

@@ -1,5 +1,6 @@
 // ps_kernels_select.hpp — deep top-k (64 < K <= PS_MAX_DEEP_TOPK): k_deep_offsets + K4s k_deep_select, and result
-// pages (ranks [skip, skip + K) for skip > 0): K4w k_deep_window, a two-sided form of the same select (at the end).
+// pages (ranks [skip, skip + K) for skip > 0): K4w k_deep_window, a two-sided form of the same select; and, at the end,
+// Kt k_deep_threshold, which runs INSIDE stage 1 and lets its second launch emit only what can reach rank skip + K.
 //
 // Stage 1 is full-result mode's (k_score<.., FULL> / k_z21<true>): every query's run of (doc, score) behind
 // full_off / full_cnt.  k_deep_select then picks the first K of the run's canonical order (score desc, doc asc)
@@ -48,6 +49,7 @@ struct DeepParams {
   double* out_scores;
   uint32_t* out_counts;
   uint32_t K, row0;
+  unsigned long long* run_results;  // ps_work_counters::run_results: every query adds the length of the run it selects from
 };
 
 // Run offsets of a deep batch on the device: off[q] = sum over earlier queries of min(n_docs, sum of list lengths) -
@@ -180,9 +182,10 @@ __device__ __forceinline__ void select_pass(const uint64_t* src_s, const uint32_
 
 // The pivot bin of the histogram for `need` elements from the top: ctl->pivot, ->above (elements in higher bins),
 // ->pop (elements in it) - or ->pivot2, ->above2, ->pop2 for `second`.  need >= 1 and the histogram holds at least
-// `need`.  Ends with a barrier.
+// `need`.  Ends with a barrier.  NT: threads of the workgroup (k_deep_threshold's is narrower).
+template <int NT = DEEP_NT>
 __device__ __forceinline__ void find_pivot(const uint32_t* hist, const uint32_t need, Ctl* ctl, const bool second = false) {
-  constexpr int PER = DEEP_BINS / DEEP_NT;
+  constexpr int PER = DEEP_BINS / NT;
   const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
   const int top = DEEP_BINS - 1 - (int)threadIdx.x * PER;  // this thread's bins: top, top - 1, ... (descending digits)
   uint32_t h[PER], mine = 0;
@@ -210,8 +213,9 @@ __device__ __forceinline__ void find_pivot(const uint32_t* hist, const uint32_t 
   __syncthreads();
 }
 
+template <int NT = DEEP_NT>
 __device__ __forceinline__ void clear_hist(uint32_t* hist) {
-  for (int b = threadIdx.x; b < DEEP_BINS; b += DEEP_NT) hist[b] = 0u;
+  for (int b = threadIdx.x; b < DEEP_BINS; b += NT) hist[b] = 0u;
 }
 
 // The end of both select kernels: bitonic sort of the n_win winners (LDS), padded to a power of two with keys below
@@ -261,7 +265,7 @@ __global__ __launch_bounds__(DEEP_NT) void k_deep_select(const DeepParams a) {
   const uint64_t off = a.off[q];
   const uint64_t n = min((uint64_t)a.cnt[q], a.off[q + 1] - off);
   uint32_t n_out = (uint32_t)min((uint64_t)K, n);
-  if (threadIdx.x == 0) { ctl->n_win = 0; ctl->n_dst = 0; }
+  if (threadIdx.x == 0) { ctl->n_win = 0; ctl->n_dst = 0; atomicAdd(a.run_results, (unsigned long long)n); }
   clear_hist(hist);
   __syncthreads();
 
@@ -347,7 +351,7 @@ __global__ __launch_bounds__(DEEP_NT) void k_deep_window(const DeepParams a, con
   const uint64_t hi = min(n, (uint64_t)skip + K);
   const uint32_t n_out = skip < n ? (uint32_t)(hi - skip) : 0u;
   uint32_t n_win = 0, first = 0;  // winners to sort; where the window begins among them
-  if (threadIdx.x == 0) { ctl->n_win = 0; ctl->n_dst = 0; }
+  if (threadIdx.x == 0) { ctl->n_win = 0; ctl->n_dst = 0; atomicAdd(a.run_results, (unsigned long long)n); }
   clear_hist(hist);
   __syncthreads();
 
@@ -453,6 +457,98 @@ __global__ __launch_bounds__(DEEP_NT) void k_deep_window(const DeepParams a, con
   }
   __syncthreads();
   sort_and_write(a, q, win_s, win_d, n_win, first, n_out);
+}
+
+// Kt: k_deep_threshold - between the two launches of a thresholded stage 1 (ps_engine.hip: score_into_runs).  The run
+// holds what the first launch emitted: every match among the documents of the first runs.  thr[q] = the bit pattern of
+// the hi-th largest SCORE of that run (hi = skip + top_k), +0.0 when the run holds fewer than hi: a lower bound of the
+// query's final hi-th best score, so the second launch may drop every document that scores strictly below it.
+// One workgroup per query, an MSD counting descent as in K4s but over the 63 score bits alone - scores repeat, so the
+// descent always takes its six levels (12 / 12 / 12 / 12 / 12 / 3 bits) and ends on one value, not on one element - and
+// it only counts: no winners, no sort, no doc ids, no global scratch.  The first pass histograms level 0 of the whole
+// run; every later level is one pass over the candidates - the run, filtered by the pivot prefix, until the pivot bin
+// fits the LDS candidate buffer (that pass compacts it: scores only), the LDS buffer from then on.  A bin that never
+// fits (a long block of equal scores) is re-filtered in place on every level, which is K4s's tie rule.
+// THR_NT = 512: the run is a sample (about 1/16 of the query's matches), a pass is a few loads per lane, and what is
+// left - six pivot searches over 4096 bins and the barriers around them - is cheaper with 8 waves than with 16.
+// LDS: histogram 16 KiB | candidate scores 56 KiB | control: 73 856 B, so two workgroups share a CU's 160 KiB.
+constexpr int THR_NT = 512;
+constexpr int THR_LEVELS = 6;
+constexpr int THR_CAND = 7168;
+constexpr size_t THR_LDS = (size_t)DEEP_BINS * 4 + (size_t)THR_CAND * 8 + 128;
+static_assert(DEEP_BINS % THR_NT == 0 && THR_NT / WAVE <= DEEP_WAVES && sizeof(deep::Ctl) <= 128 && 2 * THR_LDS <= 160 * 1024,
+              "k_deep_threshold's LDS plan");
+
+namespace deep {
+// One pass over src[0, m) (the run, or the LDS candidates): the scores that match `pre` go into the histogram of
+// hist_lvl and, when there is one, to dst (dst_cap elements).  Every thread of the workgroup calls with the same arguments.
+__device__ __forceinline__ void threshold_pass(const uint64_t* src, const uint64_t m, const Prefix pre, const int hist_lvl,
+                                               uint64_t* dst, const uint32_t dst_cap, uint32_t* hist, Ctl* ctl) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const Level gh = level_of(hist_lvl);
+  for (uint64_t base = 0; base < m; base += (uint64_t)THR_NT * DEEP_U) {
+    uint64_t s[DEEP_U];
+#pragma unroll
+    for (int u = 0; u < DEEP_U; ++u) {
+      const uint64_t i = base + (uint64_t)u * THR_NT + threadIdx.x;
+      s[u] = i < m ? src[i] : 0ull;
+    }
+#pragma unroll
+    for (int u = 0; u < DEEP_U; ++u) {
+      const uint64_t i = base + (uint64_t)u * THR_NT + threadIdx.x;
+      const bool act = i < m && (s[u] & pre.s_mask) == pre.s_val;
+      if (dst != nullptr) {
+        const uint32_t o = wave_slot(&ctl->n_dst, lane, act);
+        if (act && o < dst_cap) dst[o] = s[u];
+      }
+      hist_add(hist, lane, act, digit_of(gh, s[u], 0u));
+    }
+  }
+}
+}  // namespace deep
+
+__global__ __launch_bounds__(THR_NT) void k_deep_threshold(const uint64_t* run_score, const uint64_t* off, const uint32_t* cnt,
+                                                           const uint32_t hi, unsigned long long* thr) {
+  using namespace deep;
+  extern __shared__ __align__(16) unsigned char deep_lds[];
+  uint32_t* hist = reinterpret_cast<uint32_t*>(deep_lds);
+  uint64_t* cand = reinterpret_cast<uint64_t*>(deep_lds + (size_t)DEEP_BINS * 4);
+  Ctl* ctl = reinterpret_cast<Ctl*>(cand + THR_CAND);
+
+  const uint32_t q = blockIdx.x;
+  const uint64_t o = off[q];
+  const uint64_t n = min((uint64_t)cnt[q], off[q + 1] - o);
+  if (n < (uint64_t)hi) {  // the sample cannot bound the hi-th best: the second launch emits everything
+    if (threadIdx.x == 0) thr[q] = 0ull;
+    return;
+  }
+  const uint64_t* run = run_score + o;
+  if (threadIdx.x == 0) ctl->n_dst = 0;
+  clear_hist<THR_NT>(hist);
+  __syncthreads();
+  Prefix pre;
+  threshold_pass(run, n, pre, 0, nullptr, 0u, hist, ctl);
+  __syncthreads();
+  uint64_t m = n;  // candidates once they sit in LDS
+  bool in_lds = false;
+  uint32_t need = hi;
+  for (int lvl = 0;; ++lvl) {
+    find_pivot<THR_NT>(hist, need, ctl);
+    const uint32_t pivot = ctl->pivot, pop = ctl->pop;
+    need -= ctl->above;
+    pre.push(level_of(lvl), pivot);
+    if (lvl == THR_LEVELS - 1) break;
+    const bool to_lds = !in_lds && pop <= (uint32_t)THR_CAND;
+    __syncthreads();  // every thread has read ctl and the histogram
+    clear_hist<THR_NT>(hist);
+    if (threadIdx.x == 0) ctl->n_dst = 0;
+    __syncthreads();
+    if (in_lds) threshold_pass(cand, m, pre, lvl + 1, nullptr, 0u, hist, ctl);
+    else threshold_pass(run, n, pre, lvl + 1, to_lds ? cand : nullptr, pop, hist, ctl);
+    if (to_lds) { m = pop; in_lds = true; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) thr[q] = pre.s_val;  // all 63 score bits are pivot digits now
 }
 
 }  // namespace ps
