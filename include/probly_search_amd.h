@@ -124,9 +124,24 @@ typedef struct ps_score_callbacks {
 } ps_score_callbacks;
 
 enum { PS_SCORER_BM25 = 1, PS_SCORER_ZERO_TO_ONE = 2, PS_SCORER_HOST_CALLBACKS = 3 };
+/* How a query's terms combine.  PS_MATCH_ANY is the reference's query: every token separator is a disjunction
+ * (src/query.rs:20).  PS_MATCH_ALL ("all of these words"): for a query with the non-empty tokens t_0 .. t_{n-1}
+ * (the tokenizer's output, duplicates kept) the result is the PS_MATCH_ANY result list restricted to the documents
+ * that are in the PS_MATCH_ANY result list of every t_i queried alone - scores and order are the OR query's, bit
+ * for bit.  A document matches a term iff it is alive and a posting of one of the term's lists (expansions,
+ * version and delta layers) scores Some, i.e. > 0 (bm25.rs:89-92), under the call's scorer and fields_boost; a
+ * query without a non-empty token, or with a token that has no list, has no results.  The mode travels in the
+ * descriptor, so EVERY entry point that takes one honours it: ps_snapshot_query, ps_index_query,
+ * ps_snapshot_query_batch[_page], ps_snapshot_query_batch_device*, .._device_page_flat,
+ * ps_snapshot_query_batch_allgather*, ps_snapshot_count_batch* (totals of the intersection);
+ * ps_snapshot_plan_ahead_flat answers *accepted = 0 (match-all batches are planned on the host and scored by
+ * k_conj, an intersect-and-score kernel, for every top_k).  BM25 only: PS_SCORER_ZERO_TO_ONE or
+ * PS_SCORER_HOST_CALLBACKS with PS_MATCH_ALL is PS_EUNSUPPORTED, as are more than 64 non-empty terms in one
+ * match-all query (any number of expanded lists).  Any other match_mode value is PS_EINVAL. */
+enum { PS_MATCH_ANY = 0, PS_MATCH_ALL = 1 };
 typedef struct ps_scorer_desc {
   int32_t kind;   /* PS_SCORER_*                                                        */
-  int32_t _pad;
+  int32_t match_mode; /* PS_MATCH_*; 0 = PS_MATCH_ANY (the field was padding before ABI 10: callers wrote 0) */
   double bm25_k1; /* BM25::bm25k1, default 1.2  (src/score/default/bm25.rs:14-26)       */
   double bm25_b;  /* BM25::bm25b,  default 0.75                                         */
   const ps_score_callbacks* callbacks; /* PS_SCORER_HOST_CALLBACKS only (else NULL).  Accepted by
@@ -149,8 +164,9 @@ int ps_device_count(void);
  * 6: ps_kernel_times.score_busy_ms (round 5), ps_comm_all_gather (round 6).
  * 7: the result-page entry points (ps_snapshot_query_batch_page, .._device_page_flat, .._allgather_page_flat).
  * 8: the match-count entry points (ps_snapshot_count_batch, ps_snapshot_count_batch_device_flat).
- * 9: ps_work_counters.run_results (thresholded stage 1 of deep top-k and result pages). */
-#define PS_ABI_VERSION 9u
+ * 9: ps_work_counters.run_results (thresholded stage 1 of deep top-k and result pages).
+ * 10: ps_scorer_desc.match_mode (was _pad; PS_MATCH_ALL: conjunctive queries). */
+#define PS_ABI_VERSION 10u
 uint32_t ps_abi_version(void);
 /* Run-time options by name.  A value set here wins over the environment variable of the same name; engines read their options when
  * they are created and again at the next batch after any ps_set_option.  The list (PS_EINVAL for any other name):

@@ -18,7 +18,7 @@ class PsError(RuntimeError):
 
 PS_OK, PS_EINVAL, PS_ENOMEM, PS_EHIP, PS_EUNSUPPORTED, PS_ENODEVICE, PS_ERCCL = range(7)
 PS_COMM_ID_BYTES = 128
-PS_ABI_VERSION = 9  # include/probly_search_amd.h
+PS_ABI_VERSION = 10  # include/probly_search_amd.h
 
 
 class Str(C.Structure):
@@ -65,7 +65,7 @@ class ScoreCallbacks(C.Structure):
 
 
 class ScorerDesc(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("_pad", C.c_int32), ("bm25_k1", C.c_double), ("bm25_b", C.c_double),
+    _fields_ = [("kind", C.c_int32), ("match_mode", C.c_int32), ("bm25_k1", C.c_double), ("bm25_b", C.c_double),
                 ("callbacks", C.POINTER(ScoreCallbacks))]
 
 

@@ -63,6 +63,9 @@ ps_status fail(ps_status s, const char* msg) {
 
 ps_status check_query_args(const ps_snapshot* snap, const ps_scorer_desc* sc, const double* boosts, size_t n_boost) {
   if (!snap || !sc) return fail(PS_EINVAL, "null snapshot or scorer");
+  if (sc->match_mode != PS_MATCH_ANY && sc->match_mode != PS_MATCH_ALL) return fail(PS_EINVAL, "unknown match_mode");
+  if (sc->match_mode == PS_MATCH_ALL && (sc->kind == PS_SCORER_ZERO_TO_ONE || sc->kind == PS_SCORER_HOST_CALLBACKS))
+    return fail(PS_EUNSUPPORTED, "match-all (PS_MATCH_ALL) is served for PS_SCORER_BM25 only");
   if (sc->kind == PS_SCORER_HOST_CALLBACKS)
     return fail(PS_EINVAL, "PS_SCORER_HOST_CALLBACKS walks the host index in the reference's list order: use ps_index_query");
   if (sc->kind != PS_SCORER_BM25 && sc->kind != PS_SCORER_ZERO_TO_ONE) return fail(PS_EINVAL, "unknown scorer kind");
@@ -121,6 +124,7 @@ void plan_batch(ps_snapshot* snap, const ps_scorer_desc& sc, const std::vector<s
     for (size_t i = 1; i < pl.qbeg.size(); ++i) plan.qbeg.push_back(base + pl.qbeg[i]);
     plan.qterms_len.insert(plan.qterms_len.end(), pl.qterms_len.begin(), pl.qterms_len.end());
     plan.n_nodes.insert(plan.n_nodes.end(), pl.n_nodes.begin(), pl.n_nodes.end());
+    plan.n_qterms.insert(plan.n_qterms.end(), pl.n_qterms.begin(), pl.n_qterms.end());
     plan.postings += pl.postings;
     plan.max_entries = std::max(plan.max_entries, pl.max_entries);
     plan.max_qterms = std::max(plan.max_qterms, pl.max_qterms);
@@ -171,7 +175,9 @@ ps_status run_device_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const
     // hands the text over and sizes the launches from the plan's totals
     // (zero_to_one: the batches K1dz takes; run_device_planned hands the others back before anything is enqueued)
     // (a result page, skip > 0, is planned on the host like any deep batch)
-    if (!skip && !tokenizer && snap && scorer && (scorer->kind == PS_SCORER_BM25 || scorer->kind == PS_SCORER_ZERO_TO_ONE) && snap->engine &&
+    // (and so is a match-all batch)
+    if (!skip && !tokenizer && snap && scorer && scorer->match_mode == PS_MATCH_ANY &&
+        (scorer->kind == PS_SCORER_BM25 || scorer->kind == PS_SCORER_ZERO_TO_ONE) && snap->engine &&
         top_k >= 1 && top_k <= PS_MAX_DEVICE_TOPK && offsets && snap->engine->wants_device_plan(n_queries)) {
       ps_status st = check_query_args(snap, scorer, fields_boost, n_boost);
       if (st != PS_OK) return st;
@@ -595,6 +601,8 @@ ps_status ps_index_query(ps_index* idx, const ps_scorer_desc* scorer, const char
     return guard([&]() -> ps_status {
       if (!out || !out_len) return fail(PS_EINVAL, "null argument");
       if (!scorer->callbacks) return fail(PS_EINVAL, "PS_SCORER_HOST_CALLBACKS without callbacks");
+      if (scorer->match_mode != PS_MATCH_ANY && scorer->match_mode != PS_MATCH_ALL) return fail(PS_EINVAL, "unknown match_mode");
+      if (scorer->match_mode == PS_MATCH_ALL) return fail(PS_EUNSUPPORTED, "match-all (PS_MATCH_ALL) is served for PS_SCORER_BM25 only");
       if (n_boost < idx->idx.fields_len() || (idx->idx.fields_len() && !fields_boost))
         return fail(PS_EINVAL, "fields_boost shorter than fields_num");
       std::vector<ps_result> res;
@@ -637,6 +645,7 @@ ps_status ps_snapshot_plan_ahead_flat(ps_snapshot* snap, const ps_scorer_desc* s
   return guard([&]() -> ps_status {
     if (!snap || !scorer || (n_queries && (!text || !offsets))) return fail(PS_EINVAL, "null argument");
     if (!snap->engine) return fail(PS_ENODEVICE, "host-only snapshot");
+    if (scorer->match_mode != PS_MATCH_ANY && scorer->match_mode != PS_MATCH_ALL) return fail(PS_EINVAL, "unknown match_mode");
     const bool ok = snap->engine->plan_ahead(*scorer, text, offsets, n_queries);
     if (accepted) *accepted = ok ? 1 : 0;
     return PS_OK;

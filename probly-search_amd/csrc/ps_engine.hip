@@ -183,6 +183,8 @@ struct Tuning {
   uint32_t score_alt = 1;        // PS_SCORE_ALT: consecutive K1d batches alternate between the scoring stream and a second one at the LOWEST stream priority (1) - a hardware queue of its own, whose kernel fills what the other's tail leaves free (two streams of one priority share a queue and serialise: 3); 0: one scoring stream; 2: everything on the low-priority stream; 4: three-way rotation normal / low / high.  Round 5, same box: C2 0.3025 -> 0.289 ms per step, C3 0.363 -> 0.312, C4 1.118 -> 0.940, C5 1.585 -> 1.213
   uint32_t device_plan = 1;      // PS_DEVICE_PLAN: flat BM25 top-k batches (built-in tokenizer) are planned by k_plan on the device
   uint32_t count_window_log2 = 0;  // PS_COUNT_WINDOW_LOG2: documents per window of Kc k_count_matches (0: count_window_log2's rule; 8..19)
+  uint32_t conj_chunk = CONJ_CHUNK;  // PS_CONJ_CHUNK: driver postings per work item of Kj k_conj (1..CONJ_NT, one per lane)
+  uint32_t conj_lists = CONJ_LISTS;  // PS_CONJ_LISTS: plan entries whose sub-ranges Kj k_conj keeps in LDS at a time (1..CONJ_LISTS)
   uint32_t deep_sample_runs = 0;   // PS_DEEP_SAMPLE_RUNS: runs of a deep / paged stage 1 scored in front of k_deep_threshold (0: deep_sample_runs' rule; n: exactly n, at most n_super - 1; 0xFFFFFFFF: never threshold)
   void load();
 };
@@ -218,6 +220,7 @@ struct EngineImpl {
   // per-batch device buffers (grow-only; reuse is ordered by the stream)
   DevBuf<unsigned char> d_stage;  // plan entries + per-query arrays, uploaded once per batch (k_upload)
   DevBuf<unsigned char> d_count;  // enqueue_count: lists | qbeg | items
+  DevBuf<unsigned char> d_conj;   // stage_conj: entries | qbeg | order | terms per query | items
   DevBuf<unsigned long long> d_count_totals;  // ... and the totals of a call that wants them on the host
   DevBuf<uint32_t> d_cand_doc, d_full_doc, d_full_cnt;
   DevBuf<double> d_cand_score, d_full_score;
@@ -779,7 +782,7 @@ void Engine::work_counters(ps_work_counters& out, bool reset) {
     for (uint32_t k = 0; k < WS_WORDS; ++k) sum[k] += w[(size_t)sl * WS_WORDS + k];
   memset(&out, 0, sizeof(out));
   out.launches = m.wc_launches;
-  out.items = m.wc_items;
+  out.items = m.wc_items + sum[WS_ITEMS];  // (Kj k_conj counts its items itself)
   out.items_run = sum[WS_ITEMS_RUN];
   out.postings_scanned = sum[WS_SCANNED];
   out.postings_reached_lookups = sum[WS_REACHED];
@@ -968,6 +971,8 @@ void Tuning::load() {
     z21_exact_numerator = env_u32("PS_Z21_EXACT_NUMERATOR", z21_exact_numerator);
     count_window_log2 = env_u32("PS_COUNT_WINDOW_LOG2", count_window_log2);
     deep_sample_runs = env_u32("PS_DEEP_SAMPLE_RUNS", deep_sample_runs);
+    conj_chunk = std::max(1u, std::min((uint32_t)CONJ_NT, env_u32("PS_CONJ_CHUNK", conj_chunk)));
+    conj_lists = std::max(1u, std::min(CONJ_LISTS, env_u32("PS_CONJ_LISTS", conj_lists)));
 }
 
 namespace {
@@ -984,6 +989,13 @@ void validate(const Snapshot& s, const ps_scorer_desc& sc, const Plan& plan) {
   if (s.F > (uint32_t)MAX_F) throw std::length_error("the GPU path supports at most 8 fields");
   if (sc.kind != PS_SCORER_BM25 && sc.kind != PS_SCORER_ZERO_TO_ONE) throw std::invalid_argument("unknown scorer kind");
   if (plan.max_qterms >= 0x7FFF) throw std::length_error("more than 32766 non-empty terms in one query");
+  if (sc.match_mode != PS_MATCH_ANY && sc.match_mode != PS_MATCH_ALL) throw std::invalid_argument("unknown match_mode");
+  if (sc.match_mode == PS_MATCH_ALL) {
+    if (sc.kind != PS_SCORER_BM25) throw std::length_error("match-all (PS_MATCH_ALL) is served for BM25 only");
+    if (plan.n_qterms.size() + 1 != plan.qbeg.size()) throw std::invalid_argument("match-all needs a host-planned batch");
+    for (uint32_t nt : plan.n_qterms)
+      if (nt > CONJ_MAX_TERMS) throw std::length_error("match-all: more than 64 non-empty terms in one query");
+  }
 }
 
 // Uploads the plan + per-query arrays through a pinned staging slot; fills the common KParams.
@@ -2791,6 +2803,7 @@ Plan sub_plan(const Plan& plan, size_t b, size_t e) {
     p2.qbeg.push_back((uint32_t)p2.entries.size());
     p2.qterms_len.push_back(plan.qterms_len[q]);
     p2.n_nodes.push_back(plan.n_nodes[q]);
+    if (q < plan.n_qterms.size()) p2.n_qterms.push_back(plan.n_qterms[q]);
   }
   p2.max_entries = plan.max_entries;
   p2.max_qterms = plan.max_qterms;
@@ -2843,6 +2856,91 @@ uint32_t deep_sample_runs(const EngineImpl& m, const Plan& plan, uint32_t n_supe
   return std::min(std::max((uint32_t)std::ceil(f * n_super), 1u), n_super / 2);
 }
 
+// Stage 1 of a match-all slice (sc.match_mode == PS_MATCH_ALL, BM25): Kj k_conj (ps_kernels_conj.hpp) instead of the
+// streaming kernels, into the same runs.  The work items are built HERE from the host plan, as enqueue_count's are: the
+// plan is on the host and the item count sizes the grid.  Per query: its entries grouped by query term (a term's entries
+// follow each other in the plan); THE DRIVER RULE: the term with the smallest sum of list lengths drives, the lowest
+// ordinal on a tie; a query with no non-empty term, or with a term that has no posting, gets no item - its run stays
+// empty; every list of the driver term is cut into chunks of PS_CONJ_CHUNK postings, one item each.  `order` lists the
+// query's entries for phase A: the driver term's first, then the other terms in ascending total length.  Entries, qbeg,
+// order, terms per query and items go up in one copy from a pinned slot, fenced by the slot's event.
+// count_runs: no select kernel follows that would add the runs' lengths to ps_work_counters::run_results.
+void conj_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, hipStream_t st, bool count_runs) {
+  const size_t B = plan.qbeg.size() - 1, ne = plan.entries.size();
+  refresh_tuning(m);
+  m.last_bounds_recomputed = false;
+  const uint32_t chunk = m.tune.conj_chunk;
+  std::vector<uint32_t> order(ne);
+  std::vector<ConjItem> items;
+  std::vector<uint64_t> tot;
+  std::vector<uint32_t> first, terms;
+  for (size_t q = 0; q < B; ++q) {
+    const uint32_t e0 = plan.qbeg[q], e1 = plan.qbeg[q + 1], nt = plan.n_qterms[q];
+    for (uint32_t e = e0; e < e1; ++e) order[e] = e;
+    if (!nt) continue;
+    tot.assign(nt, 0);
+    first.assign(nt + 1, e1);  // first[t]: the term's first entry (its last is in front of first[t + 1]'s)
+    for (uint32_t e = e1; e-- > e0;) {
+      tot[plan.entries[e].qterm] += plan.entries[e].len;
+      first[plan.entries[e].qterm] = e;
+    }
+    for (uint32_t t = nt; t-- > 0;) first[t] = std::min(first[t], first[t + 1]);  // (a term without entries: an empty range)
+    if (*std::min_element(tot.begin(), tot.end()) == 0) continue;
+    const uint32_t drv = (uint32_t)(std::min_element(tot.begin(), tot.end()) - tot.begin());
+    terms.clear();
+    for (uint32_t t = 0; t < nt; ++t) terms.push_back(t);
+    std::stable_sort(terms.begin(), terms.end(), [&](uint32_t x, uint32_t y) { return (x == drv) != (y == drv) ? x == drv : tot[x] < tot[y]; });
+    uint32_t at = e0;
+    for (uint32_t t : terms)
+      for (uint32_t e = first[t]; e < first[t + 1]; ++e) order[at++] = e;
+    for (uint32_t e = first[drv]; e < first[drv + 1]; ++e)
+      for (uint64_t b = 0; b < plan.entries[e].len; b += chunk)
+        items.push_back(ConjItem{(uint32_t)q, e, (uint32_t)b, (uint32_t)std::min<uint64_t>(chunk, plan.entries[e].len - b)});
+  }
+  if (items.size() >= 0x7FFFFFF0ull) throw std::length_error("match-all batch too large for one launch");
+  wait_daat_contexts(m, st);
+  const size_t off_q = ne * sizeof(ps_plan_entry), off_o = off_q + (B + 1) * 4, off_t = off_o + ne * 4,
+               off_i = (off_t + B * 4 + 15) & ~(size_t)15, total = off_i + items.size() * sizeof(ConjItem);
+  Stage& sg = claim_stage(m);
+  sg.ensure(total + 16);
+  if (ne) memcpy(sg.p, plan.entries.data(), ne * sizeof(ps_plan_entry));
+  memcpy(sg.p + off_q, plan.qbeg.data(), (B + 1) * 4);
+  if (ne) memcpy(sg.p + off_o, order.data(), ne * 4);
+  memcpy(sg.p + off_t, plan.n_qterms.data(), B * 4);
+  if (!items.empty()) memcpy(sg.p + off_i, items.data(), items.size() * sizeof(ConjItem));
+  m.d_conj.ensure(total + 16);
+  PS_HIP(hipMemcpyAsync(m.d_conj.p, sg.p, total, hipMemcpyHostToDevice, st));
+  fence_stage(sg, st);
+  KParams kp;
+  fill_common_kparams(m, sc, boosts, B, plan.max_qterms, kp);
+  kp.plan = reinterpret_cast<const ps_plan_entry*>(m.d_conj.p);
+  kp.qbeg = reinterpret_cast<const uint32_t*>(m.d_conj.p + off_q);
+  kp.K = 1;
+  kp.full_doc = m.d_full_doc.p;
+  kp.full_score = m.d_full_score.p;
+  kp.full_off = m.d_full_off.p;
+  kp.full_cnt = m.d_full_cnt.p;
+  ConjParams cp{};
+  cp.order = reinterpret_cast<const uint32_t*>(m.d_conj.p + off_o);
+  cp.n_terms = reinterpret_cast<const uint32_t*>(m.d_conj.p + off_t);
+  cp.items = reinterpret_cast<const ConjItem*>(m.d_conj.p + off_i);
+  cp.run_results = count_runs ? m.d_wstats + WS_RUN_RESULTS : nullptr;
+  cp.lists = m.tune.conj_lists;
+  hipLaunchKernelGGL(k_deep_offsets, dim3(1), dim3(DEEP_NT), 0, st, kp.plan, kp.qbeg, kp.B, kp.n_docs, m.d_full_off.p, m.d_full_cnt.p);
+  PS_HIP(hipGetLastError());
+  m.last_layout_bytes = 0;
+  m.last_rows = m.last_rows_built = 0;
+  EngineImpl::KTimer* kt = begin_timer(m, st);
+  PS_HIP(hipEventRecord(kt->m, st));  // (no K0 / K0b in front of this kernel)
+  if (!items.empty()) {
+    m.wc_launches++;
+    m.score_kernel_name = "ps::k_conj";
+    hipLaunchKernelGGL(k_conj, dim3((uint32_t)items.size()), dim3(CONJ_NT), 0, st, kp, cp);
+    PS_HIP(hipGetLastError());
+  }
+  end_timer(m, kt, st);
+}
+
 // Stage 1 of one slice on `st`, into the run buffers (ensure_runs; the caller has joined the tail): the plan is staged, the
 // runs are laid out and their counts cleared (k_deep_offsets), K0 / K0b + the scoring kernel run in the timer bracket, and
 // the staging slot, if the kernels read it in place, is fenced behind them.
@@ -2855,6 +2953,10 @@ uint32_t deep_sample_runs(const EngineImpl& m, const Plan& plan, uint32_t n_supe
 // bm25_params_sane; other parameters keep the single launch.
 void score_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, hipStream_t st,
                      uint32_t hi = 0) {
+  if (sc.match_mode == PS_MATCH_ALL) {  // one launch, no k_deep_threshold pass: conjunctive runs are short
+    conj_into_runs(m, sc, boosts, plan, st, hi == 0);
+    return;
+  }
   KParams kp;
   EngineImpl::KTimer* kt = nullptr;
   try {
@@ -2979,6 +3081,7 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
 enum CountRoute { COUNT_FAST, COUNT_FAST_ZB, COUNT_SLOW };
 CountRoute count_route(const Snapshot& s, const ps_scorer_desc& sc, const double* boosts, uint32_t* pos_fields) {
   *pos_fields = 0;
+  if (sc.match_mode == PS_MATCH_ALL) return COUNT_SLOW;  // an intersection, not a union: Kj k_conj's run lengths
   if (sc.kind == PS_SCORER_ZERO_TO_ONE) return COUNT_FAST;
   if (!(std::isfinite(sc.bm25_k1) && sc.bm25_k1 >= 0.0 && sc.bm25_k1 <= 1e100 && sc.bm25_b >= 0.0 && sc.bm25_b <= 1.0)) return COUNT_SLOW;
   bool zero = false;
@@ -3312,6 +3415,7 @@ bool Engine::plan_ahead(const ps_scorer_desc& sc, const char* text, const uint64
   EngineImpl& m = *impl_;
   const bool z = sc.kind == PS_SCORER_ZERO_TO_ONE;
   if ((sc.kind != PS_SCORER_BM25 && !z) || m.snap->F > (uint32_t)MAX_F) return false;
+  if (sc.match_mode != PS_MATCH_ANY) return false;  // match-all batches are planned on the host
   std::lock_guard<std::mutex> lock(m.mu);
   PS_HIP(hipSetDevice(m.device));
   refresh_tuning(m);
@@ -3354,6 +3458,7 @@ bool Engine::run_device_planned(const ps_scorer_desc& sc, const double* boosts, 
   if (s.F > (uint32_t)MAX_F) throw std::length_error("the GPU path supports at most 8 fields");
   if (top_k < 1 || top_k > PS_MAX_DEEP_TOPK) throw std::invalid_argument("top_k must be in [1, 1024] for the device top-k path");
   if (top_k > PS_MAX_DEVICE_TOPK) return false;  // the deep top-k path is planned on the host (run_device)
+  if (sc.match_mode != PS_MATCH_ANY) return false;  // so is a match-all batch (Kj k_conj's items are built from the host plan)
   std::lock_guard<std::mutex> lock(m.mu);
   PS_HIP(hipSetDevice(m.device));
   refresh_tuning(m);
@@ -3486,7 +3591,7 @@ void Engine::run_device(const ps_scorer_desc& sc, const double* boosts, const Pl
   const double t0 = now_ms();
   hipStream_t st = stream ? (hipStream_t)stream : m.stream;
   const OutBlock out = out_block(d_keys, d_scores, d_counts);
-  if (skip || top_k > PS_MAX_DEVICE_TOPK) enqueue_deep(m, sc, boosts, plan, skip, top_k, out, st);
+  if (skip || sc.match_mode == PS_MATCH_ALL || top_k > PS_MAX_DEVICE_TOPK) enqueue_deep(m, sc, boosts, plan, skip, top_k, out, st);
   else enqueue_topk(m, sc, boosts, plan, top_k, out, st, false);
   memset(&stats, 0, sizeof(stats));
   fill_stats(m, stats, s, plan, (uint64_t)(plan.qbeg.size() - 1) * top_k);
@@ -3544,7 +3649,7 @@ void Engine::run_host(const ps_scorer_desc& sc, const double* boosts, const Plan
 
   if (top_k >= 1 && top_k <= PS_MAX_DEEP_TOPK) {
     // k_deep_select (a page: k_deep_window) instead of the scoring kernels' own top-k: the same block
-    const bool deep = skip || top_k > PS_MAX_DEVICE_TOPK;
+    const bool deep = skip || sc.match_mode == PS_MATCH_ALL || top_k > PS_MAX_DEVICE_TOPK;
     std::lock_guard<std::mutex> lock(m.mu);
     PS_HIP(hipSetDevice(m.device));
     hipStream_t st = m.stream;

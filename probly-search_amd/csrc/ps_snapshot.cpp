@@ -952,6 +952,7 @@ void Snapshot::plan_query(const ps_scorer_desc& sc, std::string_view q, ps_token
   plan.qbeg.push_back((uint32_t)plan.entries.size());
   plan.qterms_len.push_back((uint32_t)tokens.size());
   plan.n_nodes.push_back((uint32_t)seen_nodes.size());
+  plan.n_qterms.push_back(qord);
   plan.max_entries = std::max<uint32_t>(plan.max_entries, (uint32_t)(plan.entries.size() - e_begin));
   plan.max_qterms = std::max(plan.max_qterms, qord);
   plan.max_nodes = std::max<uint32_t>(plan.max_nodes, (uint32_t)seen_nodes.size());

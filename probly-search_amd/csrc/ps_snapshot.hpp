@@ -58,6 +58,7 @@ struct Plan {
   std::vector<uint32_t> qbeg;          // per query: first entry; size B+1
   std::vector<uint32_t> qterms_len;    // per query: TermData::query_terms_len
   std::vector<uint32_t> n_nodes;       // per query: distinct nodes (zero_to_one)
+  std::vector<uint32_t> n_qterms;      // per query: non-empty terms, with or without lists (host planner; match-all needs every one of them matched)
   uint64_t postings = 0;               // sum of entry lens
   uint32_t max_entries = 0, max_qterms = 0, max_nodes = 0;
   bool multi_expansion = false;        // some query term owns >1 entry -> visited tags needed
