@@ -139,6 +139,19 @@ enum { PS_SCORER_BM25 = 1, PS_SCORER_ZERO_TO_ONE = 2, PS_SCORER_HOST_CALLBACKS =
  * PS_SCORER_HOST_CALLBACKS with PS_MATCH_ALL is PS_EUNSUPPORTED, as are more than 64 non-empty terms in one
  * match-all query (any number of expanded lists).  Any other match_mode value is PS_EINVAL. */
 enum { PS_MATCH_ANY = 0, PS_MATCH_ALL = 1 };
+/* A query-time document filter: an allow-list of document keys (a tenant, a category, an access list), resolved once
+ * on the snapshot's device by ps_snapshot_filter_new and named by ps_scorer_desc::filter.  A filtered result is the
+ * unfiltered result list of the same call restricted to the allowed keys - scores and order are the unfiltered
+ * query's, bit for bit; N, df, idf and the field averages stay corpus-wide.  The filter travels in the descriptor,
+ * so every query and count entry point of a snapshot honours it, in both match modes and for both built-in scorers
+ * (one filter per call; totals of ps_snapshot_count_batch* are those of the filtered lists).  A filtered batch is
+ * always planned on the host: ps_snapshot_plan_ahead_flat answers *accepted = 0, ps_snapshot_plan[_device] ignore
+ * the field, ps_index_query (whose snapshot is private) answers PS_EINVAL.  Stage 1 is either driven by the filter
+ * (BM25: k_filter_score looks the filter's documents up in the query's lists) or by the lists under the filter's
+ * bitmap, whichever touches less (PS_FILTER_DRIVE).  A filter belongs to the snapshot AND the state it was made
+ * from: on another snapshot, or after a ps_snapshot_update that changed the snapshot (mode != 0), a call that names
+ * it is PS_EINVAL - create it again. */
+typedef struct ps_filter ps_filter;
 typedef struct ps_scorer_desc {
   int32_t kind;   /* PS_SCORER_*                                                        */
   int32_t match_mode; /* PS_MATCH_*; 0 = PS_MATCH_ANY (the field was padding before ABI 10: callers wrote 0) */
@@ -147,6 +160,7 @@ typedef struct ps_scorer_desc {
   const ps_score_callbacks* callbacks; /* PS_SCORER_HOST_CALLBACKS only (else NULL).  Accepted by
                      ps_index_query (the entry that owns the posting lists in the reference's
                      order); the snapshot entry points return PS_EINVAL for it.             */
+  const ps_filter* filter; /* NULL = no filter; else the call's results are restricted to the filter's documents (ABI 11) */
 } ps_scorer_desc;
 
 const char* ps_last_error(void);
@@ -165,8 +179,9 @@ int ps_device_count(void);
  * 7: the result-page entry points (ps_snapshot_query_batch_page, .._device_page_flat, .._allgather_page_flat).
  * 8: the match-count entry points (ps_snapshot_count_batch, ps_snapshot_count_batch_device_flat).
  * 9: ps_work_counters.run_results (thresholded stage 1 of deep top-k and result pages).
- * 10: ps_scorer_desc.match_mode (was _pad; PS_MATCH_ALL: conjunctive queries). */
-#define PS_ABI_VERSION 10u
+ * 10: ps_scorer_desc.match_mode (was _pad; PS_MATCH_ALL: conjunctive queries).
+ * 11: ps_scorer_desc.filter (trailing field), ps_snapshot_filter_new / ps_filter_free / ps_filter_len. */
+#define PS_ABI_VERSION 11u
 uint32_t ps_abi_version(void);
 /* Run-time options by name.  A value set here wins over the environment variable of the same name; engines read their options when
  * they are created and again at the next batch after any ps_set_option.  The list (PS_EINVAL for any other name):
@@ -421,6 +436,16 @@ ps_status ps_snapshot_count_batch_device_flat(ps_snapshot* snap, const ps_scorer
                                               const uint64_t* offsets, size_t n_queries, const double* fields_boost,
                                               size_t n_boost, ps_tokenizer_fn tokenizer, void* user, void* d_totals,
                                               void* hip_stream);
+
+/* Document filters (see ps_filter above).  ps_snapshot_filter_new resolves `keys` - any order, duplicates allowed, keys
+ * the snapshot does not hold are ignored; n_keys = 0 (keys may then be NULL) is a valid filter that matches nothing -
+ * on the snapshot's device: one copy up, k_filter_build (a binary search per key in the doc-id -> key plane, the alive
+ * bitmap ANDed in, a scan-and-scatter into the sorted doc-id list), one word down (the length).  PS_EINVAL: null snap /
+ * out, or keys with n_keys > 0; PS_ENODEVICE: a host-only snapshot.  ps_filter_len: the alive documents of the snapshot
+ * the filter selects.  ps_filter_free: NULL is fine; a filter may outlive its snapshot (it is then of no use). */
+ps_status ps_snapshot_filter_new(ps_snapshot* snap, const uint64_t* keys, size_t n_keys, ps_filter** out);
+void ps_filter_free(ps_filter* f);
+uint64_t ps_filter_len(const ps_filter* f);
 
 /* ---- multi-GPU: replicated corpus, query batch sharded across ranks, RCCL all-gather of top-k ----
  * Queries are independent (each Index::query owns its scores / visited maps, src/query.rs:31,37),

@@ -18,7 +18,7 @@ class PsError(RuntimeError):
 
 PS_OK, PS_EINVAL, PS_ENOMEM, PS_EHIP, PS_EUNSUPPORTED, PS_ENODEVICE, PS_ERCCL = range(7)
 PS_COMM_ID_BYTES = 128
-PS_ABI_VERSION = 10  # include/probly_search_amd.h
+PS_ABI_VERSION = 11  # include/probly_search_amd.h
 
 
 class Str(C.Structure):
@@ -66,7 +66,7 @@ class ScoreCallbacks(C.Structure):
 
 class ScorerDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("match_mode", C.c_int32), ("bm25_k1", C.c_double), ("bm25_b", C.c_double),
-                ("callbacks", C.POINTER(ScoreCallbacks))]
+                ("callbacks", C.POINTER(ScoreCallbacks)), ("filter", C.c_void_p)]
 
 
 class UpdateStats(C.Structure):
@@ -177,6 +177,9 @@ SYMBOLS = {
                                           C.c_size_t, _P, _P, _P]),
     "ps_snapshot_count_batch_device_flat": (C.c_int, [_P, C.POINTER(ScorerDesc), _P, _P, C.c_size_t,
                                                       C.POINTER(C.c_double), C.c_size_t, _P, _P, _P, _P]),
+    "ps_snapshot_filter_new": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(_P)]),
+    "ps_filter_free": (None, [_P]),
+    "ps_filter_len": (C.c_uint64, [_P]),
     "ps_snapshot_query_batch_device_planned_flat": (C.c_int, [_P, C.POINTER(ScorerDesc), _P, _P, C.c_size_t,
                                                               C.POINTER(C.c_double), C.c_size_t, C.c_size_t, _P, _P,
                                                               _P, _P]),

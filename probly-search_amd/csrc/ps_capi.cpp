@@ -175,8 +175,8 @@ ps_status run_device_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const
     // hands the text over and sizes the launches from the plan's totals
     // (zero_to_one: the batches K1dz takes; run_device_planned hands the others back before anything is enqueued)
     // (a result page, skip > 0, is planned on the host like any deep batch)
-    // (and so is a match-all batch)
-    if (!skip && !tokenizer && snap && scorer && scorer->match_mode == PS_MATCH_ANY &&
+    // (and so are a match-all batch and a filtered one)
+    if (!skip && !tokenizer && snap && scorer && scorer->match_mode == PS_MATCH_ANY && !scorer->filter &&
         (scorer->kind == PS_SCORER_BM25 || scorer->kind == PS_SCORER_ZERO_TO_ONE) && snap->engine &&
         top_k >= 1 && top_k <= PS_MAX_DEVICE_TOPK && offsets && snap->engine->wants_device_plan(n_queries)) {
       ps_status st = check_query_args(snap, scorer, fields_boost, n_boost);
@@ -596,6 +596,7 @@ ps_status ps_index_query(ps_index* idx, const ps_scorer_desc* scorer, const char
                          const double* fields_boost, size_t n_boost, ps_tokenizer_fn tokenizer, void* user,
                          size_t top_k, ps_result** out, size_t* out_len) {
   if (!idx) return fail(PS_EINVAL, "null index");
+  if (scorer && scorer->filter) return fail(PS_EINVAL, "ps_index_query's snapshot is private: a filter is made from, and used with, a ps_snapshot");
   if (scorer && scorer->kind == PS_SCORER_HOST_CALLBACKS) {
     // a custom ScoreCalculator: the reference's driver loop on the host, the callbacks do the scoring
     return guard([&]() -> ps_status {
@@ -708,6 +709,18 @@ ps_status ps_snapshot_count_batch_device_flat(ps_snapshot* snap, const ps_scorer
     return run_count(snap, scorer, qs, fields_boost, n_boost, tokenizer, user, d_totals, nullptr, hip_stream);
   });
 }
+
+ps_status ps_snapshot_filter_new(ps_snapshot* snap, const uint64_t* keys, size_t n_keys, ps_filter** out) {
+  return guard([&]() -> ps_status {
+    if (!snap || !out || (n_keys && !keys)) return fail(PS_EINVAL, "null argument");
+    if (!snap->engine) return fail(PS_ENODEVICE, "host-only snapshot: a filter is resolved on the snapshot's device");
+    *out = snap->engine->filter_new(keys, n_keys);
+    return PS_OK;
+  });
+}
+
+void ps_filter_free(ps_filter* f) { ps::filter_free(f); }
+uint64_t ps_filter_len(const ps_filter* f) { return f ? f->len : 0; }
 
 ps_status ps_snapshot_query_batch_device_planned_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const char* text,
                                                       const uint64_t* offsets, size_t n_queries, const double* fields_boost,

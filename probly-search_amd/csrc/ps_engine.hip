@@ -73,6 +73,7 @@ namespace ps {
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+static std::atomic<uint64_t> g_state_serial{1};  // EngineImpl::state: no two engine states of a process share a value
 static std::atomic<uint64_t> g_opt_gen{1};  // bumped by every ps_set_option: engines re-read their knobs at the next batch
 template <typename T>
 struct DevBuf {
@@ -185,6 +186,8 @@ struct Tuning {
   uint32_t count_window_log2 = 0;  // PS_COUNT_WINDOW_LOG2: documents per window of Kc k_count_matches (0: count_window_log2's rule; 8..19)
   uint32_t conj_chunk = CONJ_CHUNK;  // PS_CONJ_CHUNK: driver postings per work item of Kj k_conj (1..CONJ_NT, one per lane)
   uint32_t conj_lists = CONJ_LISTS;  // PS_CONJ_LISTS: plan entries whose sub-ranges Kj k_conj keeps in LDS at a time (1..CONJ_LISTS)
+  uint32_t filter_chunk = FILTER_CHUNK;  // PS_FILTER_CHUNK: filter documents per work item of Kf k_filter_score (1..CONJ_NT, one per lane)
+  uint32_t filter_drive = 2;       // PS_FILTER_DRIVE: which stage 1 a filtered BM25 slice takes (0: the lists drive, under the allow bitmap; 1: the filter drives, Kf k_filter_score; else THE DRIVER RULE of score_into_runs)
   uint32_t deep_sample_runs = 0;   // PS_DEEP_SAMPLE_RUNS: runs of a deep / paged stage 1 scored in front of k_deep_threshold (0: deep_sample_runs' rule; n: exactly n, at most n_super - 1; 0xFFFFFFFF: never threshold)
   void load();
 };
@@ -204,6 +207,7 @@ struct EngineImpl {
   uint32_t* d_table = nullptr;
   uint32_t* d_bits = nullptr;
   uint32_t* d_alive = nullptr;  // one bit per doc id (delta removals)
+  uint64_t state = g_state_serial.fetch_add(1);  // what a ps_filter is bound to: renewed whenever the documents or their ids change (apply_delta)
   DevBuf<unsigned long long> d_removed_df;  // per layer, scratch of count_removed_df
   uint64_t* d_keys = nullptr;
   double* d_lut = nullptr;
@@ -690,6 +694,7 @@ void Engine::apply_delta(const DeltaRanges& r, std::vector<uint64_t>& removed_df
   PS_HIP(hipSetDevice(m.device));
   PS_HIP(hipDeviceSynchronize());  // no batch of this snapshot is in flight while its planes change
   m.aheads.clear();                // (batches announced ahead were counted against the old trie: their query calls plan again)
+  m.state = g_state_serial.fetch_add(1);  // filters made from the old state are refused from here on
   uint64_t up = 0;
   auto put = [&](void* dst, const void* src, size_t bytes) {
     if (!bytes) return;
@@ -746,6 +751,60 @@ void Engine::apply_delta(const DeltaRanges& r, std::vector<uint64_t>& removed_df
     PS_HIP(hipMemcpy(removed_df.data(), d_out, nl * 8, hipMemcpyDeviceToHost));
   }
   if (bytes_uploaded) *bytes_uploaded = up;
+}
+
+// k_filter_build (ps_kernels_filter.hpp): keys up in one copy, mark -> count (AND alive) -> scan -> scatter on the engine's
+// stream, the length down.  The doc list has room for min(n_keys, n_ids) documents: more cannot be hit.
+ps_filter* Engine::filter_new(const uint64_t* keys, size_t n_keys) {
+  EngineImpl& m = *impl_;
+  const Snapshot& s = *m.snap;
+  std::lock_guard<std::mutex> lock(m.mu);
+  PS_HIP(hipSetDevice(m.device));
+  const uint32_t n_words = (uint32_t)s.alive.size(), n_blocks = (n_words + FILTER_NT - 1) / FILTER_NT;
+  std::unique_ptr<ps_filter, void (*)(ps_filter*)> f(new ps_filter(), &filter_free);
+  f->state = m.state;
+  f->device = m.device;
+  const size_t room = std::min<uint64_t>(n_keys, s.n_ids);
+  PS_HIP(hipMalloc((void**)&f->d_allow, std::max<size_t>(1, n_words) * 4));
+  PS_HIP(hipMalloc((void**)&f->d_docs, (room + 1) * 4));
+  PS_HIP(hipMemsetAsync(f->d_allow, 0, std::max<size_t>(1, n_words) * 4, m.stream));
+  if (n_keys && n_words) {
+    uint64_t* d_in = nullptr;
+    uint32_t* d_tot = nullptr;  // [n_blocks] workgroup totals, then their prefix sums | the grand total
+    PS_HIP(hipMalloc((void**)&d_in, n_keys * 8));
+    hipError_t e = hipMalloc((void**)&d_tot, ((size_t)n_blocks + 1) * 4);
+    uint32_t len = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in, keys, n_keys * 8, hipMemcpyHostToDevice, m.stream);
+    if (e == hipSuccess) {
+      const uint32_t grid = (uint32_t)std::min<uint64_t>((n_keys + FILTER_NT - 1) / FILTER_NT, 65536);
+      hipLaunchKernelGGL(k_filter_mark, dim3(grid), dim3(FILTER_NT), 0, m.stream, d_in, (uint64_t)n_keys, m.d_keys, (uint32_t)s.n_ids, f->d_allow);
+      hipLaunchKernelGGL(k_filter_count, dim3(n_blocks), dim3(FILTER_NT), 0, m.stream, f->d_allow, m.d_alive, n_words, d_tot);
+      hipLaunchKernelGGL(k_filter_scan, dim3(1), dim3(FILTER_NT), 0, m.stream, d_tot, n_blocks, d_tot + n_blocks);
+      hipLaunchKernelGGL(k_filter_scatter, dim3(n_blocks), dim3(FILTER_NT), 0, m.stream, f->d_allow, n_words, d_tot, f->d_docs);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&len, d_tot + n_blocks, 4, hipMemcpyDeviceToHost, m.stream);
+    const hipError_t e2 = hipStreamSynchronize(m.stream);
+    (void)hipFree(d_in);
+    (void)hipFree(d_tot);
+    PS_HIP(e);
+    PS_HIP(e2);
+    f->len = len;
+  } else {
+    PS_HIP(hipStreamSynchronize(m.stream));
+  }
+  return f.release();
+}
+
+void filter_free(ps_filter* f) {
+  if (!f) return;
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  if (f->device >= 0) (void)hipSetDevice(f->device);
+  if (f->d_allow) (void)hipFree(f->d_allow);
+  if (f->d_docs) (void)hipFree(f->d_docs);
+  if (cur >= 0) (void)hipSetDevice(cur);
+  delete f;
 }
 
 uint64_t Engine::device_bytes() const { return impl_->bytes; }
@@ -973,6 +1032,8 @@ void Tuning::load() {
     deep_sample_runs = env_u32("PS_DEEP_SAMPLE_RUNS", deep_sample_runs);
     conj_chunk = std::max(1u, std::min((uint32_t)CONJ_NT, env_u32("PS_CONJ_CHUNK", conj_chunk)));
     conj_lists = std::max(1u, std::min(CONJ_LISTS, env_u32("PS_CONJ_LISTS", conj_lists)));
+    filter_chunk = std::max(1u, std::min((uint32_t)CONJ_NT, env_u32("PS_FILTER_CHUNK", filter_chunk)));
+    filter_drive = env_u32("PS_FILTER_DRIVE", filter_drive);
 }
 
 namespace {
@@ -983,6 +1044,19 @@ void refresh_tuning(EngineImpl& m) {
   if (m.tune_gen == g) return;
   m.tune.load();
   m.tune_gen = g;
+}
+
+// The bitmap stage 1 drops documents by when it emits: the call's allow bitmap (alive AND filter), else the alive bitmap
+// when a delta removed anything.  Nothing kept across batches has it baked in: dense rows, list bounds and the LUT are
+// functions of the postings; every kernel reads the bitmap when it emits.
+const uint32_t* emit_bitmap(const EngineImpl& m, const ps_scorer_desc& sc) {
+  return sc.filter ? sc.filter->d_allow : m.snap->any_dead ? m.d_alive : nullptr;
+}
+
+// A filter serves the engine and the state it was resolved on (the doc ids and the alive set it holds are that state's).
+void check_filter(const EngineImpl& m, const ps_scorer_desc& sc) {
+  if (sc.filter && sc.filter->state != m.state)
+    throw std::invalid_argument("the filter was made from another snapshot, or before ps_snapshot_update changed this one: create it again");
 }
 
 void validate(const Snapshot& s, const ps_scorer_desc& sc, const Plan& plan) {
@@ -1955,7 +2029,7 @@ void stage_plan(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, c
 
   memset(&kp, 0, sizeof(kp));
   kp.doc = m.d_doc; kp.tf = m.d_tf; kp.fl = m.d_fl; kp.tfl = m.d_tfl; kp.table = m.d_table; kp.keys = m.d_keys; kp.bits = m.d_bits;
-  kp.alive = s.any_dead ? m.d_alive : nullptr;
+  kp.alive = emit_bitmap(m, sc);
   kp.plan = reinterpret_cast<const ps_plan_entry*>(dbase + off_e);
   kp.qbeg = reinterpret_cast<const uint32_t*>(dbase + off_q);
   kp.qterms_len = reinterpret_cast<const uint32_t*>(dbase + off_l);
@@ -2865,53 +2939,52 @@ uint32_t deep_sample_runs(const EngineImpl& m, const Plan& plan, uint32_t n_supe
 // query's entries for phase A: the driver term's first, then the other terms in ascending total length.  Entries, qbeg,
 // order, terms per query and items go up in one copy from a pinned slot, fenced by the slot's event.
 // count_runs: no select kernel follows that would add the runs' lengths to ps_work_counters::run_results.
-void conj_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, hipStream_t st, bool count_runs) {
-  const size_t B = plan.qbeg.size() - 1, ne = plan.entries.size();
-  refresh_tuning(m);
-  m.last_bounds_recomputed = false;
-  const uint32_t chunk = m.tune.conj_chunk;
-  std::vector<uint32_t> order(ne);
-  std::vector<ConjItem> items;
-  std::vector<uint64_t> tot;
-  std::vector<uint32_t> first, terms;
-  for (size_t q = 0; q < B; ++q) {
-    const uint32_t e0 = plan.qbeg[q], e1 = plan.qbeg[q + 1], nt = plan.n_qterms[q];
-    for (uint32_t e = e0; e < e1; ++e) order[e] = e;
-    if (!nt) continue;
-    tot.assign(nt, 0);
-    first.assign(nt + 1, e1);  // first[t]: the term's first entry (its last is in front of first[t + 1]'s)
-    for (uint32_t e = e1; e-- > e0;) {
-      tot[plan.entries[e].qterm] += plan.entries[e].len;
-      first[plan.entries[e].qterm] = e;
-    }
-    for (uint32_t t = nt; t-- > 0;) first[t] = std::min(first[t], first[t + 1]);  // (a term without entries: an empty range)
-    if (*std::min_element(tot.begin(), tot.end()) == 0) continue;
-    const uint32_t drv = (uint32_t)(std::min_element(tot.begin(), tot.end()) - tot.begin());
-    terms.clear();
-    for (uint32_t t = 0; t < nt; ++t) terms.push_back(t);
-    std::stable_sort(terms.begin(), terms.end(), [&](uint32_t x, uint32_t y) { return (x == drv) != (y == drv) ? x == drv : tot[x] < tot[y]; });
-    uint32_t at = e0;
-    for (uint32_t t : terms)
-      for (uint32_t e = first[t]; e < first[t + 1]; ++e) order[at++] = e;
-    for (uint32_t e = first[drv]; e < first[drv + 1]; ++e)
-      for (uint64_t b = 0; b < plan.entries[e].len; b += chunk)
-        items.push_back(ConjItem{(uint32_t)q, e, (uint32_t)b, (uint32_t)std::min<uint64_t>(chunk, plan.entries[e].len - b)});
+struct TermOrder {
+  std::vector<uint64_t> tot;           // postings per query term
+  std::vector<uint32_t> first, terms;  // first[t]: the term's first entry (its last is in front of first[t + 1]'s); terms: ascending tot
+};
+// Query q's entries into order[qbeg[q] ..), term by term in ascending total length (the lowest ordinal first on a tie:
+// terms[0] is the driver term).  false - and the plan's own order - when the conjunction is empty whatever the documents.
+bool order_by_term(const Plan& plan, size_t q, TermOrder& t, std::vector<uint32_t>& order) {
+  const uint32_t e0 = plan.qbeg[q], e1 = plan.qbeg[q + 1], nt = plan.n_qterms[q];
+  for (uint32_t e = e0; e < e1; ++e) order[e] = e;
+  if (!nt) return false;
+  t.tot.assign(nt, 0);
+  t.first.assign(nt + 1, e1);
+  for (uint32_t e = e1; e-- > e0;) {
+    t.tot[plan.entries[e].qterm] += plan.entries[e].len;
+    t.first[plan.entries[e].qterm] = e;
   }
-  if (items.size() >= 0x7FFFFFF0ull) throw std::length_error("match-all batch too large for one launch");
+  for (uint32_t x = nt; x-- > 0;) t.first[x] = std::min(t.first[x], t.first[x + 1]);  // (a term without entries: an empty range)
+  if (*std::min_element(t.tot.begin(), t.tot.end()) == 0) return false;
+  t.terms.clear();
+  for (uint32_t x = 0; x < nt; ++x) t.terms.push_back(x);
+  std::stable_sort(t.terms.begin(), t.terms.end(), [&](uint32_t x, uint32_t y) { return t.tot[x] < t.tot[y]; });
+  uint32_t at = e0;
+  for (uint32_t x : t.terms)
+    for (uint32_t e = t.first[x]; e < t.first[x + 1]; ++e) order[at++] = e;
+  return true;
+}
+
+// What Kj and Kf read beside the planes: entries | qbeg | order | terms per query | `tail` (Kj: its items; Kf: its query
+// list) in one copy from a pinned slot into d_conj; the common KParams; the runs laid out (k_deep_offsets).
+struct ConjBlock { const uint32_t *order, *n_terms; const unsigned char* tail; };
+ConjBlock stage_conj(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, const std::vector<uint32_t>& order,
+                     const void* tail, size_t tail_bytes, hipStream_t st, KParams& kp) {
+  const size_t B = plan.qbeg.size() - 1, ne = plan.entries.size();
   wait_daat_contexts(m, st);
   const size_t off_q = ne * sizeof(ps_plan_entry), off_o = off_q + (B + 1) * 4, off_t = off_o + ne * 4,
-               off_i = (off_t + B * 4 + 15) & ~(size_t)15, total = off_i + items.size() * sizeof(ConjItem);
+               off_i = (off_t + B * 4 + 15) & ~(size_t)15, total = off_i + tail_bytes;
   Stage& sg = claim_stage(m);
   sg.ensure(total + 16);
   if (ne) memcpy(sg.p, plan.entries.data(), ne * sizeof(ps_plan_entry));
   memcpy(sg.p + off_q, plan.qbeg.data(), (B + 1) * 4);
   if (ne) memcpy(sg.p + off_o, order.data(), ne * 4);
   memcpy(sg.p + off_t, plan.n_qterms.data(), B * 4);
-  if (!items.empty()) memcpy(sg.p + off_i, items.data(), items.size() * sizeof(ConjItem));
+  if (tail_bytes) memcpy(sg.p + off_i, tail, tail_bytes);
   m.d_conj.ensure(total + 16);
   PS_HIP(hipMemcpyAsync(m.d_conj.p, sg.p, total, hipMemcpyHostToDevice, st));
   fence_stage(sg, st);
-  KParams kp;
   fill_common_kparams(m, sc, boosts, B, plan.max_qterms, kp);
   kp.plan = reinterpret_cast<const ps_plan_entry*>(m.d_conj.p);
   kp.qbeg = reinterpret_cast<const uint32_t*>(m.d_conj.p + off_q);
@@ -2920,16 +2993,37 @@ void conj_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boost
   kp.full_score = m.d_full_score.p;
   kp.full_off = m.d_full_off.p;
   kp.full_cnt = m.d_full_cnt.p;
-  ConjParams cp{};
-  cp.order = reinterpret_cast<const uint32_t*>(m.d_conj.p + off_o);
-  cp.n_terms = reinterpret_cast<const uint32_t*>(m.d_conj.p + off_t);
-  cp.items = reinterpret_cast<const ConjItem*>(m.d_conj.p + off_i);
-  cp.run_results = count_runs ? m.d_wstats + WS_RUN_RESULTS : nullptr;
-  cp.lists = m.tune.conj_lists;
   hipLaunchKernelGGL(k_deep_offsets, dim3(1), dim3(DEEP_NT), 0, st, kp.plan, kp.qbeg, kp.B, kp.n_docs, m.d_full_off.p, m.d_full_cnt.p);
   PS_HIP(hipGetLastError());
   m.last_layout_bytes = 0;
   m.last_rows = m.last_rows_built = 0;
+  return ConjBlock{reinterpret_cast<const uint32_t*>(m.d_conj.p + off_o), reinterpret_cast<const uint32_t*>(m.d_conj.p + off_t), m.d_conj.p + off_i};
+}
+
+void conj_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, hipStream_t st, bool count_runs) {
+  const size_t B = plan.qbeg.size() - 1, ne = plan.entries.size();
+  refresh_tuning(m);
+  m.last_bounds_recomputed = false;
+  const uint32_t chunk = m.tune.conj_chunk;
+  std::vector<uint32_t> order(ne);
+  std::vector<ConjItem> items;
+  TermOrder t;
+  for (size_t q = 0; q < B; ++q) {
+    if (!order_by_term(plan, q, t, order)) continue;
+    const uint32_t drv = t.terms[0];
+    for (uint32_t e = t.first[drv]; e < t.first[drv + 1]; ++e)
+      for (uint64_t b = 0; b < plan.entries[e].len; b += chunk)
+        items.push_back(ConjItem{(uint32_t)q, e, (uint32_t)b, (uint32_t)std::min<uint64_t>(chunk, plan.entries[e].len - b)});
+  }
+  if (items.size() >= 0x7FFFFFF0ull) throw std::length_error("match-all batch too large for one launch");
+  KParams kp;
+  const ConjBlock blk = stage_conj(m, sc, boosts, plan, order, items.data(), items.size() * sizeof(ConjItem), st, kp);
+  ConjParams cp{};
+  cp.order = blk.order;
+  cp.n_terms = blk.n_terms;
+  cp.items = reinterpret_cast<const ConjItem*>(blk.tail);
+  cp.run_results = count_runs ? m.d_wstats + WS_RUN_RESULTS : nullptr;
+  cp.lists = m.tune.conj_lists;
   EngineImpl::KTimer* kt = begin_timer(m, st);
   PS_HIP(hipEventRecord(kt->m, st));  // (no K0 / K0b in front of this kernel)
   if (!items.empty()) {
@@ -2939,6 +3033,62 @@ void conj_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boost
     PS_HIP(hipGetLastError());
   }
   end_timer(m, kt, st);
+}
+
+// Stage 1 of a filtered BM25 slice whose filter drives (score_into_runs' DRIVER RULE): Kf k_filter_score
+// (ps_kernels_filter.hpp), both match modes, into the same runs.  One item per (query that can have a result, chunk of
+// PS_FILTER_CHUNK documents of the filter's doc list): the kernel finds its item from blockIdx, so only the list of such
+// queries goes up, with the block Kj reads.  Match-any: every query with a plan entry, phase A in plan order.  Match-all:
+// the queries order_by_term accepts, phase A in its order.
+void filter_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, hipStream_t st, bool count_runs) {
+  const size_t B = plan.qbeg.size() - 1, ne = plan.entries.size();
+  const ps_filter& f = *sc.filter;
+  const bool all = sc.match_mode == PS_MATCH_ALL;
+  refresh_tuning(m);
+  m.last_bounds_recomputed = false;
+  std::vector<uint32_t> order(ne), queries;
+  TermOrder t;
+  for (size_t q = 0; q < B; ++q) {
+    if (all ? order_by_term(plan, q, t, order) : plan.qbeg[q + 1] > plan.qbeg[q]) queries.push_back((uint32_t)q);
+    if (!all) for (uint32_t e = plan.qbeg[q]; e < plan.qbeg[q + 1]; ++e) order[e] = e;
+  }
+  const uint32_t chunk = m.tune.filter_chunk;
+  const uint64_t n_chunks = (f.len + chunk - 1) / chunk, n_items = n_chunks * queries.size();
+  if (n_items >= 0x7FFFFFF0ull) throw std::length_error("filtered batch too large for one launch");
+  KParams kp;
+  const ConjBlock blk = stage_conj(m, sc, boosts, plan, order, queries.data(), queries.size() * 4, st, kp);
+  FilterParams fp{};
+  fp.order = blk.order;
+  fp.n_terms = blk.n_terms;
+  fp.queries = reinterpret_cast<const uint32_t*>(blk.tail);
+  fp.docs = f.d_docs;
+  fp.run_results = count_runs ? m.d_wstats + WS_RUN_RESULTS : nullptr;
+  fp.n_docs = (uint32_t)f.len;
+  fp.chunk = chunk;
+  fp.n_chunks = (uint32_t)n_chunks;
+  fp.lists = m.tune.conj_lists;
+  EngineImpl::KTimer* kt = begin_timer(m, st);
+  PS_HIP(hipEventRecord(kt->m, st));  // (no K0 / K0b in front of this kernel)
+  if (n_items) {
+    m.wc_launches++;
+    m.score_kernel_name = "ps::k_filter_score";
+    if (all) hipLaunchKernelGGL(k_filter_score<true>, dim3((uint32_t)n_items), dim3(CONJ_NT), 0, st, kp, fp);
+    else hipLaunchKernelGGL(k_filter_score<false>, dim3((uint32_t)n_items), dim3(CONJ_NT), 0, st, kp, fp);
+    PS_HIP(hipGetLastError());
+  }
+  end_timer(m, kt, st);
+}
+
+// THE DRIVER RULE of a filtered slice: the filter drives - Kf looks its documents up in the lists - when the slice's
+// queries x the filter's documents are fewer than R x the postings the lists would stream; both routes do a bounded
+// amount of work per driver element.  R = 2 / 5, measured (EXPERIMENTS.md, first section: 256 C2 queries): Kf spends
+// 73 - 81 ps per (query, filter document), the streaming kernel 36 ps per posting, so the routes cross at 0.44; R = 1
+// sent the 5 % filter to Kf, 1.34 ms against 0.96.  BM25 only (zero_to_one has no filter-driven kernel: its lists drive).
+constexpr uint64_t FILTER_DRIVE_R_NUM = 2, FILTER_DRIVE_R_DEN = 5;
+bool filter_drives(const EngineImpl& m, const ps_scorer_desc& sc, const Plan& plan) {
+  if (!sc.filter || sc.kind != PS_SCORER_BM25 || m.tune.filter_drive == 0) return false;
+  if (m.tune.filter_drive == 1) return true;
+  return FILTER_DRIVE_R_DEN * (uint64_t)(plan.qbeg.size() - 1) * sc.filter->len < FILTER_DRIVE_R_NUM * plan.postings;
 }
 
 // Stage 1 of one slice on `st`, into the run buffers (ensure_runs; the caller has joined the tail): the plan is staged, the
@@ -2953,6 +3103,13 @@ void conj_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boost
 // bm25_params_sane; other parameters keep the single launch.
 void score_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, hipStream_t st,
                      uint32_t hi = 0) {
+  if (sc.filter) {
+    refresh_tuning(m);
+    if (filter_drives(m, sc, plan)) {  // one launch, no k_deep_threshold pass: nothing is streamed that a threshold could drop
+      filter_into_runs(m, sc, boosts, plan, st, hi == 0);
+      return;
+    }
+  }
   if (sc.match_mode == PS_MATCH_ALL) {  // one launch, no k_deep_threshold pass: conjunctive runs are short
     conj_into_runs(m, sc, boosts, plan, st, hi == 0);
     return;
@@ -3145,7 +3302,7 @@ void enqueue_count(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts
     CountParams cp{};
     cp.doc = m.d_doc;
     cp.tf = m.d_tf;
-    cp.alive = s.any_dead ? m.d_alive : nullptr;
+    cp.alive = emit_bitmap(m, sc);
     cp.lists = reinterpret_cast<const CountList*>(m.d_count.p);
     cp.qbeg = reinterpret_cast<const uint32_t*>(m.d_count.p + off_q);
     cp.items = reinterpret_cast<const CountItem*>(m.d_count.p + off_i);
@@ -3362,7 +3519,7 @@ void fill_common_kparams(EngineImpl& m, const ps_scorer_desc& sc, const double* 
   const Snapshot& s = *m.snap;
   memset(&kp, 0, sizeof(kp));
   kp.doc = m.d_doc; kp.tf = m.d_tf; kp.fl = m.d_fl; kp.tfl = m.d_tfl; kp.table = m.d_table; kp.keys = m.d_keys; kp.bits = m.d_bits;
-  kp.alive = s.any_dead ? m.d_alive : nullptr;
+  kp.alive = emit_bitmap(m, sc);
   kp.work_counter = m.d_work;
   kp.wstats = m.d_wstats;
   kp.P = s.P;
@@ -3415,7 +3572,7 @@ bool Engine::plan_ahead(const ps_scorer_desc& sc, const char* text, const uint64
   EngineImpl& m = *impl_;
   const bool z = sc.kind == PS_SCORER_ZERO_TO_ONE;
   if ((sc.kind != PS_SCORER_BM25 && !z) || m.snap->F > (uint32_t)MAX_F) return false;
-  if (sc.match_mode != PS_MATCH_ANY) return false;  // match-all batches are planned on the host
+  if (sc.match_mode != PS_MATCH_ANY || sc.filter) return false;  // match-all and filtered batches are planned on the host
   std::lock_guard<std::mutex> lock(m.mu);
   PS_HIP(hipSetDevice(m.device));
   refresh_tuning(m);
@@ -3458,7 +3615,7 @@ bool Engine::run_device_planned(const ps_scorer_desc& sc, const double* boosts, 
   if (s.F > (uint32_t)MAX_F) throw std::length_error("the GPU path supports at most 8 fields");
   if (top_k < 1 || top_k > PS_MAX_DEEP_TOPK) throw std::invalid_argument("top_k must be in [1, 1024] for the device top-k path");
   if (top_k > PS_MAX_DEVICE_TOPK) return false;  // the deep top-k path is planned on the host (run_device)
-  if (sc.match_mode != PS_MATCH_ANY) return false;  // so is a match-all batch (Kj k_conj's items are built from the host plan)
+  if (sc.match_mode != PS_MATCH_ANY || sc.filter) return false;  // so are a match-all batch (Kj k_conj's items are built from the host plan) and a filtered one
   std::lock_guard<std::mutex> lock(m.mu);
   PS_HIP(hipSetDevice(m.device));
   refresh_tuning(m);
@@ -3583,6 +3740,7 @@ void Engine::run_device(const ps_scorer_desc& sc, const double* boosts, const Pl
   EngineImpl& m = *impl_;
   const Snapshot& s = *m.snap;
   validate(s, sc, plan);
+  check_filter(m, sc);
   if (top_k < 1 || top_k > PS_MAX_DEEP_TOPK)
     throw std::invalid_argument("top_k must be in [1, 1024] for the device top-k path");
   check_page(skip, top_k);
@@ -3591,7 +3749,7 @@ void Engine::run_device(const ps_scorer_desc& sc, const double* boosts, const Pl
   const double t0 = now_ms();
   hipStream_t st = stream ? (hipStream_t)stream : m.stream;
   const OutBlock out = out_block(d_keys, d_scores, d_counts);
-  if (skip || sc.match_mode == PS_MATCH_ALL || top_k > PS_MAX_DEVICE_TOPK) enqueue_deep(m, sc, boosts, plan, skip, top_k, out, st);
+  if (skip || sc.match_mode == PS_MATCH_ALL || sc.filter || top_k > PS_MAX_DEVICE_TOPK) enqueue_deep(m, sc, boosts, plan, skip, top_k, out, st);
   else enqueue_topk(m, sc, boosts, plan, top_k, out, st, false);
   memset(&stats, 0, sizeof(stats));
   fill_stats(m, stats, s, plan, (uint64_t)(plan.qbeg.size() - 1) * top_k);
@@ -3608,6 +3766,7 @@ void Engine::run_count(const ps_scorer_desc& sc, const double* boosts, const Pla
   const Snapshot& s = *m.snap;
   const size_t B = plan.qbeg.size() - 1;
   validate(s, sc, plan);
+  check_filter(m, sc);
   std::lock_guard<std::mutex> lock(m.mu);
   PS_HIP(hipSetDevice(m.device));
   const double t0 = now_ms();
@@ -3641,6 +3800,7 @@ void Engine::run_host(const ps_scorer_desc& sc, const double* boosts, const Plan
   const Snapshot& s = *m.snap;
   const size_t B = plan.qbeg.size() - 1;
   validate(s, sc, plan);
+  check_filter(m, sc);
   check_page(skip, top_k);
   out.clear();
   offsets.assign(B + 1, 0);
@@ -3649,7 +3809,7 @@ void Engine::run_host(const ps_scorer_desc& sc, const double* boosts, const Plan
 
   if (top_k >= 1 && top_k <= PS_MAX_DEEP_TOPK) {
     // k_deep_select (a page: k_deep_window) instead of the scoring kernels' own top-k: the same block
-    const bool deep = skip || sc.match_mode == PS_MATCH_ALL || top_k > PS_MAX_DEVICE_TOPK;
+    const bool deep = skip || sc.match_mode == PS_MATCH_ALL || sc.filter || top_k > PS_MAX_DEVICE_TOPK;  // (a filtered batch: the pruning kernels' priming assumes that only tombstones are missing)
     std::lock_guard<std::mutex> lock(m.mu);
     PS_HIP(hipSetDevice(m.device));
     hipStream_t st = m.stream;

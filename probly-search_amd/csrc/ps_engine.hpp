@@ -10,6 +10,15 @@
 
 #include "ps_snapshot.hpp"
 
+// The handle behind the C ABI's ps_filter: a document allow-list resolved on one engine's device (Engine::filter_new).
+struct ps_filter {
+  uint64_t state = 0;           // the engine state it was made from (Engine: a process-wide serial, renewed by apply_delta)
+  int device = -1;
+  uint32_t* d_allow = nullptr;  // allow bitmap: alive AND listed, laid out and padded like the alive bitmap
+  uint32_t* d_docs = nullptr;   // the allowed doc ids, ascending
+  uint64_t len = 0;             // their number
+};
+
 namespace ps {
 
 struct EngineImpl;
@@ -115,6 +124,11 @@ class Engine {
   void run_count(const ps_scorer_desc& sc, const double* boosts, const Plan& plan, void* d_totals, uint64_t* h_totals,
                  void* stream, ps_batch_stats& stats);
 
+  // Resolves an allow-list of keys (any order, duplicates and unknown keys allowed) on the device: k_filter_build
+  // (ps_kernels_filter.hpp).  Synchronous; the length comes down once.  A call that names the filter (ps_scorer_desc::filter)
+  // is always planned on the host; it throws std::invalid_argument unless the filter was made by THIS engine in its current state.
+  ps_filter* filter_new(const uint64_t* keys, size_t n_keys);
+
   // SURVEY 8f N2 - device-side planner (BM25 and zero_to_one, built-in tokenizer): tokenise, term lookup in the frozen
   // trie, prefix expansion and before_each run on the GPU.  plan_device copies the plan back (tests);
   // run_device_planned scores the batch without the plan ever existing on the host.
@@ -146,6 +160,7 @@ class Engine {
   EngineImpl* impl_;
 };
 
+void filter_free(ps_filter* f);  // (device memory: freed on the filter's device, whether or not its engine still exists)
 int device_count();
 // Tuning knobs by name (the PS_* names of DESIGN.md section 11); read when a snapshot's engine is created.
 void set_option(const char* name, uint32_t value);

@@ -6,6 +6,7 @@
 //   ps_kernels_select.hpp  k_deep_offsets, K4s k_deep_select, K4w k_deep_window                       (top-k for 64 < k <= 1024, result pages)
 //   ps_kernels_count.hpp   Kc k_count_matches, k_count_copy                                           (exact total match counts)
 //   ps_kernels_conj.hpp    Kj k_conj                                                                  (match-all queries: intersect-and-score stage 1)
+//   ps_kernels_filter.hpp  k_filter_build (mark, count, scan, scatter), Kf k_filter_score              (document filters: filter-driven stage 1)
 // (the device-side preparation of a K1d batch: ps_prep_kernels.hpp; zero_to_one's pruning kernel: ps_z21_daat.hpp).  Included by
 // ps_engine.hip only (one translation unit); see that file's header comment for the kernel overview and DESIGN.md section 3.
 #pragma once
@@ -16,3 +17,4 @@
 #include "ps_kernels_select.hpp"
 #include "ps_kernels_count.hpp"
 #include "ps_kernels_conj.hpp"
+#include "ps_kernels_filter.hpp"

@@ -103,6 +103,85 @@ __device__ __forceinline__ void ranges(const KParams& p, uint32_t* r_beg, uint32
   __syncthreads();
 }
 
+// Phase A's question for one entry: is the lane's document `d` among the ids doc[po + rb, po + re)?  Only the lanes
+// that `want` search.  A sub-range of up to CONJ_STAGE ids is staged in LDS first - unless no lane of the workgroup
+// wants it (the vote is also the barrier behind the last search in the stage) -, a longer one is searched in global
+// memory.  Every thread of the workgroup calls, with the same (po, rb, re).
+__device__ __forceinline__ bool member(const KParams& p, uint32_t* stage, const uint64_t po, const uint32_t rb, const uint32_t re,
+                                       const bool want, const uint32_t d, const int tid) {
+  if (re - rb <= CONJ_STAGE) {
+    if (!__syncthreads_or(want ? 1 : 0)) return false;
+    stage_ids(p.doc, stage, po + rb, po + re, tid);
+    __syncthreads();
+    const uint32_t len = re - rb;
+    return want && find<uint32_t>(stage, 0u, len, d) != len;
+  }
+  return want && find<uint64_t>(p.doc, po + rb, po + re, d) != po + re;
+}
+
+// Compaction: the documents of the live lanes into surv[0 .. n), in lane order, by a ballot prefix; returns n.
+__device__ __forceinline__ uint32_t compact(const bool live, const uint32_t d, uint32_t* surv, uint32_t* wave_n) {
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+  const unsigned long long lm = __ballot(live);
+  if (lane == 0) wave_n[wave] = (uint32_t)__popcll(lm);
+  __syncthreads();
+  uint32_t base = 0, n_surv = 0;
+  for (int w = 0; w < CONJ_WAVES; ++w) {
+    if (w < wave) base += wave_n[w];
+    n_surv += wave_n[w];
+  }
+  if (live) surv[base + (uint32_t)__popcll(lm & ((1ull << lane) - 1ull))] = d;
+  __syncthreads();
+  return n_surv;
+}
+
+// Phase B: the exact score of the survivors of an item of query q (entries e0 .. e0 + n - 1, its ranges inside the doc
+// ids [first, last] parked already when `once`), one survivor per lane, and their emission into the query's run.
+// ALL: a document is emitted iff every one of the query's n_terms terms gave it Some; else iff any posting did.
+template <bool ALL>
+__device__ __forceinline__ void score_survivors(const KParams& p, uint32_t* r_beg, uint32_t* r_end, const uint32_t* surv, const uint32_t n_surv,
+                                                const uint32_t q, const uint32_t e0, const uint32_t n, const uint32_t L, const bool once,
+                                                const uint32_t first, const uint32_t last, const uint32_t n_terms,
+                                                unsigned long long* run_results) {
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
+  if (once && (uint32_t)(wave * WAVE) >= n_surv) return;  // (a wave without a survivor; no barrier below when the ranges are there already)
+  const bool has_doc = (uint32_t)tid < n_surv;
+  const uint32_t sd = has_doc ? surv[tid] : 0u;
+  double score = 0.0;
+  bool present = false;
+  uint32_t last_term = 0xFFFFFFFFu;
+  unsigned long long some = 0ull;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!once && i % L == 0) ranges(p, r_beg, r_end, nullptr, e0 + i, min(L, n - i), first, last);  // the next block, in plan order
+    const uint32_t slot = once ? i : i % L;
+    const uint32_t rb = r_beg[slot], re = r_end[slot];
+    if (rb != re && has_doc) {
+      const ps_plan_entry e = p.plan[e0 + i];
+      const uint64_t pb = e.post_off + rb, pe = e.post_off + re;
+      const uint64_t pi = find<uint64_t>(p.doc, pb, pe, sd);
+      if (pi != pe) {
+        double s = 0.0;
+        for (uint32_t x = 0; x < p.F; ++x) {
+          const uint32_t w = p.tfl[pi * p.F + x];
+          uint32_t tfu = w >> 24, flu = w & TFL_FL_ESC;
+          tfl_exact(p, x, pi, tfu, flu);
+          if (tfu > 0) s += bm25_tfn(p, x, tfu, flu) * e.idf * p.boost[x] * e.boost;  // bm25.rs:83-86: ((tfn*idf)*boost)*expansion_boost
+        }
+        if (s > 0.0) {  // Some(score) iff score > 0 (bm25.rs:89-92); max_score_merger (query.rs:150-164)
+          score = present ? (last_term == e.qterm ? fmax(score, s) : score + s) : s;
+          present = true;
+          if (ALL) some |= 1ull << e.qterm;
+        }
+        last_term = e.qterm;  // visited even when the score was None (query.rs:87)
+      }
+    }
+  }
+  const bool emit = has_doc && (ALL ? some == (n_terms >= 64u ? ~0ull : (1ull << n_terms) - 1ull) : present);
+  const uint32_t n_emit = (uint32_t)__popcll(__ballot(emit));
+  full_emit(p, q, lane, emit, score, sd, EmitFilter{false, 0.0});
+  if (lane == 0 && n_emit && run_results != nullptr) atomicAdd(run_results, (unsigned long long)n_emit);
+}
+
 }  // namespace conj
 
 __global__ __launch_bounds__(CONJ_NT) void k_conj(const KParams p, const ConjParams a) {
@@ -110,7 +189,7 @@ __global__ __launch_bounds__(CONJ_NT) void k_conj(const KParams p, const ConjPar
   __shared__ __align__(16) uint32_t stage[CONJ_STAGE];
   __shared__ uint32_t surv[CONJ_NT];
   __shared__ uint32_t wave_n[CONJ_WAVES];
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
+  const int tid = threadIdx.x;
   const ConjItem it = a.items[blockIdx.x];
   const uint32_t e0 = p.qbeg[it.q], n = p.qbeg[it.q + 1] - e0;
   const uint32_t L = min(max(a.lists, 1u), CONJ_LISTS);
@@ -151,73 +230,16 @@ __global__ __launch_bounds__(CONJ_NT) void k_conj(const KParams p, const ConjPar
     if (rb == re) continue;
     const uint64_t po = p.plan[ei].post_off;
     const bool want = live && !found;
-    bool hit = false;
-    if (re - rb <= CONJ_STAGE) {
-      // (the vote is also the barrier behind the last search in the stage)
-      if (!__syncthreads_or(want ? 1 : 0)) continue;  // every live lane has the term already
-      conj::stage_ids(p.doc, stage, po + rb, po + re, tid);
-      __syncthreads();
-      const uint32_t len = re - rb;
-      if (want) hit = conj::find<uint32_t>(stage, 0u, len, d) != len;
-    } else if (want) {
-      hit = conj::find<uint64_t>(p.doc, po + rb, po + re, d) != po + re;
-    }
+    const bool hit = conj::member(p, stage, po, rb, re, want, d, tid);
     if (own_term) live = live && !hit;  // ownership: an earlier list of the driver term holds the document
     else found = found || hit;
   }
 
-  // ---- compaction ---------------------------------------------------------------------------------------------------
-  const unsigned long long lm = __ballot(live);
-  if (lane == 0) wave_n[wave] = (uint32_t)__popcll(lm);
-  __syncthreads();
-  uint32_t base = 0, n_surv = 0;
-  for (int w = 0; w < CONJ_WAVES; ++w) {
-    if (w < wave) base += wave_n[w];
-    n_surv += wave_n[w];
-  }
-  if (live) surv[base + (uint32_t)__popcll(lm & ((1ull << lane) - 1ull))] = d;
-  __syncthreads();
+  // ---- compaction, phase B ---------------------------------------------------------------------------------------
+  const uint32_t n_surv = conj::compact(live, d, surv, wave_n);
   if (PS_WORK_COUNTERS && tid == 0) atomicAdd(&ws[WS_REACHED], (unsigned long long)n_surv);
   if (n_surv == 0) return;
-  if (once && (uint32_t)(wave * WAVE) >= n_surv) return;  // (a wave without a survivor; no barrier below when the ranges are there already)
-
-  // ---- phase B: the exact score of a survivor -----------------------------------------------------------------------
-  const bool has_doc = (uint32_t)tid < n_surv;
-  const uint32_t sd = has_doc ? surv[tid] : 0u;
-  double score = 0.0;
-  bool present = false;
-  uint32_t last_term = 0xFFFFFFFFu;
-  unsigned long long some = 0ull;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (!once && i % L == 0) conj::ranges(p, r_beg, r_end, nullptr, e0 + i, min(L, n - i), first, last);  // the next block, in plan order
-    const uint32_t slot = once ? i : i % L;
-    const uint32_t rb = r_beg[slot], re = r_end[slot];
-    if (rb != re && has_doc) {
-      const ps_plan_entry e = p.plan[e0 + i];
-      const uint64_t pb = e.post_off + rb, pe = e.post_off + re;
-      const uint64_t pi = conj::find<uint64_t>(p.doc, pb, pe, sd);
-      if (pi != pe) {
-        double s = 0.0;
-        for (uint32_t x = 0; x < p.F; ++x) {
-          const uint32_t w = p.tfl[pi * p.F + x];
-          uint32_t tfu = w >> 24, flu = w & TFL_FL_ESC;
-          tfl_exact(p, x, pi, tfu, flu);
-          if (tfu > 0) s += bm25_tfn(p, x, tfu, flu) * e.idf * p.boost[x] * e.boost;  // bm25.rs:83-86: ((tfn*idf)*boost)*expansion_boost
-        }
-        if (s > 0.0) {  // Some(score) iff score > 0 (bm25.rs:89-92); max_score_merger (query.rs:150-164)
-          score = present ? (last_term == e.qterm ? fmax(score, s) : score + s) : s;
-          present = true;
-          some |= 1ull << e.qterm;
-        }
-        last_term = e.qterm;  // visited even when the score was None (query.rs:87)
-      }
-    }
-  }
-  const uint32_t nt = a.n_terms[it.q];
-  const bool emit = has_doc && some == (nt >= 64u ? ~0ull : (1ull << nt) - 1ull);
-  const uint32_t n_emit = (uint32_t)__popcll(__ballot(emit));
-  full_emit(p, it.q, lane, emit, score, sd, EmitFilter{false, 0.0});
-  if (lane == 0 && n_emit && a.run_results != nullptr) atomicAdd(a.run_results, (unsigned long long)n_emit);
+  conj::score_survivors<true>(p, r_beg, r_end, surv, n_surv, it.q, e0, n, L, once, first, last, a.n_terms[it.q], a.run_results);
 }
 
 }  // namespace ps

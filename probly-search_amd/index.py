@@ -68,13 +68,16 @@ def _match_mode(match):
         raise ValueError('match must be "any" or "all", not %r' % (match,)) from None
 
 
-def _scorer_desc(score_calculator, match="any"):
+def _scorer_desc(score_calculator, match="any", *, filter=None):
     mode = _match_mode(match)
+    if filter is not None and (not isinstance(filter, Filter) or not filter._h):
+        raise TypeError("filter must be an open Filter (Snapshot.filter(keys)) or None")
     kind = getattr(score_calculator, "kind", None)
     if kind not in (1, 2):
         raise TypeError("score_calculator must be score.bm25.new() or score.zero_to_one.new() here; a custom "
                         "ScoreCalculator runs through Index.query (host callbacks), not on a snapshot")
-    return _lib.ScorerDesc(kind, mode, float(score_calculator.bm25k1), float(score_calculator.bm25b), None)
+    return _lib.ScorerDesc(kind, mode, float(score_calculator.bm25k1), float(score_calculator.bm25b), None,
+                           filter._h if filter is not None else None)
 
 
 class _Documents:
@@ -196,6 +199,35 @@ def _take_results(L, out, n):
     return res
 
 
+class Filter:
+    """A document allow-list resolved on a Snapshot's device (ps_filter).  len(): the alive documents it selects."""
+
+    def __init__(self, snapshot, keys):
+        import numpy as np
+        self._L = _lib.load()
+        self._snap = snapshot  # a filter is of use with its snapshot only: keep it alive
+        arr = np.ascontiguousarray(np.asarray(list(keys) if not hasattr(keys, "dtype") else keys, dtype=np.uint64))
+        self._h = C.c_void_p()
+        try:
+            _lib.check(self._L.ps_snapshot_filter_new(snapshot._h, arr.ctypes.data if arr.size else None, arr.size, C.byref(self._h)))
+        except PsError as e:
+            _raise(e)
+
+    def __len__(self):
+        return int(self._L.ps_filter_len(self._h))
+
+    def close(self):
+        if self._h:
+            self._L.ps_filter_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Snapshot:
     """Immutable flattened CSR view of an Index, resident in HBM (ps_snapshot)."""
 
@@ -231,18 +263,24 @@ class Snapshot:
         _lib.check(L.ps_snapshot_load(os.fsencode(path), device, C.byref(h)))
         return cls(h, None)
 
+    def filter(self, keys):
+        """ps_snapshot_filter_new: an allow-list of document keys (any order, duplicates and unknown keys are fine; an
+        empty list matches nothing), resolved on the device once -> Filter, for the filter= keyword of the query and
+        count methods.  It serves this snapshot until update() changes it: then create it again."""
+        return Filter(self, keys)
+
     def info(self):
         i = _lib.SnapshotInfo()
         _lib.check(self._L.ps_snapshot_get_info(self._h, C.byref(i)))
         return {k: getattr(i, k) for k, _ in i._fields_}
 
-    def query(self, query, score_calculator, tokenizer, fields_boost, top_k=0, skip=0, match="any"):
+    def query(self, query, score_calculator, tokenizer, fields_boost, top_k=0, skip=0, match="any", filter=None):
         """skip > 0: ranks [skip, skip + top_k) of the canonical order instead of the first top_k - a result page,
         selected on the device (1 <= top_k <= 1024 then; see query_batch).  match="all": see query_batch."""
         if skip:
-            return self.query_batch([query], score_calculator, tokenizer, fields_boost, top_k, skip=skip, match=match)[0]
+            return self.query_batch([query], score_calculator, tokenizer, fields_boost, top_k, skip=skip, match=match, filter=filter)[0]
         qb = query.encode("utf-8")
-        desc = _scorer_desc(score_calculator, match)
+        desc = _scorer_desc(score_calculator, match, filter=filter)
         b, nb = _boosts(fields_boost)
         tok = _Tok(tokenizer)
         out, n = C.POINTER(_lib.Result)(), C.c_size_t()
@@ -273,16 +311,18 @@ class Snapshot:
         except PsError as e:
             _raise(e)
 
-    def query_batch(self, queries, score_calculator, tokenizer, fields_boost, top_k=0, skip=0, match="any"):
+    def query_batch(self, queries, score_calculator, tokenizer, fields_boost, top_k=0, skip=0, match="any", filter=None):
         """B independent Index::query calls in one kernel pass -> list[list[QueryResult]].
         skip > 0: every query's result page, ranks [skip, skip + top_k) of the canonical order (what slicing the full
         list gives), selected on the device however deep the page lies: 1 <= top_k <= 1024 (PS_MAX_DEEP_TOPK) and
         skip + top_k <= 2**32 - 16.
         match="all" (BM25): conjunctive queries - of the match="any" result list only the documents that every
         non-empty token of the query matches when queried alone, scores and order unchanged (k_conj on the device;
-        a query with no token, or with a token that has no list, has no results).  Every batch method takes it."""
+        a query with no token, or with a token that has no list, has no results).  Every batch method takes it.
+        filter=Snapshot.filter(keys): the same result list restricted to the filter's documents, scores and order
+        unchanged (ps_scorer_desc::filter).  Every query and count method takes it, with either match mode."""
         qb, arr = self._pack_queries(queries)
-        desc = _scorer_desc(score_calculator, match)
+        desc = _scorer_desc(score_calculator, match, filter=filter)
         b, nb = _boosts(fields_boost)
         tok = _Tok(tokenizer)
         out, offs = C.POINTER(_lib.Result)(), C.POINTER(C.c_size_t)()
@@ -292,11 +332,11 @@ class Snapshot:
         self._L.ps_free(offs)
         return res
 
-    def query_batch_arrays(self, queries, score_calculator, tokenizer, fields_boost, top_k, skip=0, match="any"):
+    def query_batch_arrays(self, queries, score_calculator, tokenizer, fields_boost, top_k, skip=0, match="any", filter=None):
         """Like query_batch (skip and match included) but returns numpy arrays (keys u64[n], scores f64[n], offsets[B+1])."""
         import numpy as np
         qb, arr = self._pack_queries(queries)
-        desc = _scorer_desc(score_calculator, match)
+        desc = _scorer_desc(score_calculator, match, filter=filter)
         b, nb = _boosts(fields_boost)
         tok = _Tok(tokenizer)
         out, offs = C.POINTER(_lib.Result)(), C.POINTER(C.c_size_t)()
@@ -310,13 +350,13 @@ class Snapshot:
         return keys, scores, o
 
     def query_batch_device(self, queries, score_calculator, tokenizer, fields_boost, top_k, d_keys, d_scores,
-                           d_counts, stream=None, match="any"):
+                           d_counts, stream=None, match="any", filter=None):
         """Device-resident top-k: d_* are device pointers (ints) on this snapshot's device, e.g.
         torch tensors' data_ptr(); `stream` a hipStream_t handle (torch.cuda.Stream.cuda_stream)
         or None for the engine's own stream (synchronous).  1 <= top_k <= 1024 (PS_MAX_DEEP_TOPK; above 64 the
         deep top-k path: host planner, k_deep_select on the device - same block layout).  match: as query_batch."""
         qb, arr = self._pack_queries(queries)
-        desc = _scorer_desc(score_calculator, match)
+        desc = _scorer_desc(score_calculator, match, filter=filter)
         b, nb = _boosts(fields_boost)
         tok = _Tok(tokenizer)
         try:
@@ -327,12 +367,12 @@ class Snapshot:
             _raise(e)
 
     def query_batch_device_flat(self, text, offsets, score_calculator, fields_boost, top_k, d_keys, d_scores,
-                                d_counts, stream=None, skip=0, match="any"):
+                                d_counts, stream=None, skip=0, match="any", filter=None):
         """query_batch_device with the batch as one contiguous uint8 buffer + u64 offsets[n+1]
         (numpy arrays): no per-query marshalling on the Python side.  skip > 0: row i of the block holds ranks
         [skip, skip + top_k) of query i (ps_snapshot_query_batch_device_page_flat; limits as query_batch's).
         match: as query_batch."""
-        desc = _scorer_desc(score_calculator, match)
+        desc = _scorer_desc(score_calculator, match, filter=filter)
         b, nb = _boosts(fields_boost)
         head = (self._h, C.byref(desc), text.ctypes.data, offsets.ctypes.data, len(offsets) - 1, b, nb, None, None)
         tail = (top_k, d_keys, d_scores, d_counts, stream if stream else None)
@@ -344,14 +384,14 @@ class Snapshot:
         except PsError as e:
             _raise(e)
 
-    def count_batch(self, queries, score_calculator, fields_boost, tokenizer=None, match="any"):
+    def count_batch(self, queries, score_calculator, fields_boost, tokenizer=None, match="any", filter=None):
         """Exact total match counts -> numpy uint64[B]: totals[i] == len(query(queries[i], ..., top_k=0)), the
         reference's results.len() (src/query.rs:97-105), counted on the device (k_count_matches: a bitset union of the
         query's doc-id lists) without scoring, sorting or downloading the results.  match="all": the totals of the
         conjunctive queries (the lengths of k_conj's runs), still len() of the same call with top_k=0."""
         import numpy as np
         qb, arr = self._pack_queries(queries)
-        desc = _scorer_desc(score_calculator, match)
+        desc = _scorer_desc(score_calculator, match, filter=filter)
         b, nb = _boosts(fields_boost)
         tok = _Tok(tokenizer)
         totals = np.empty(len(qb), np.uint64)
@@ -362,10 +402,10 @@ class Snapshot:
             _raise(e)
         return totals
 
-    def count_batch_device_flat(self, text, offsets, score_calculator, fields_boost, d_totals, stream=None, match="any"):
+    def count_batch_device_flat(self, text, offsets, score_calculator, fields_boost, d_totals, stream=None, match="any", filter=None):
         """count_batch into d_totals, a device pointer (int) to u64[B] on this snapshot's device; text / offsets / stream
         as query_batch_device_flat (ps_snapshot_count_batch_device_flat).  match: as count_batch."""
-        desc = _scorer_desc(score_calculator, match)
+        desc = _scorer_desc(score_calculator, match, filter=filter)
         b, nb = _boosts(fields_boost)
         try:
             _lib.check(self._L.ps_snapshot_count_batch_device_flat(
@@ -374,24 +414,24 @@ class Snapshot:
         except PsError as e:
             _raise(e)
 
-    def _cached_args(self, score_calculator, fields_boost, match="any"):
+    def _cached_args(self, score_calculator, fields_boost, match="any", filter=None):
         """ctypes descriptor + boosts array for a serving loop that repeats the same scorer / boosts / match mode."""
-        key = (score_calculator.kind, float(score_calculator.bm25k1), float(score_calculator.bm25b), tuple(fields_boost), match)
+        key = (score_calculator.kind, float(score_calculator.bm25k1), float(score_calculator.bm25b), tuple(fields_boost), match, filter)
         hit = getattr(self, "_arg_cache", None)
         if hit is None or hit[0] != key:
             b, nb = _boosts(fields_boost)
-            hit = (key, _scorer_desc(score_calculator, match), b, nb)
+            hit = (key, _scorer_desc(score_calculator, match, filter=filter), b, nb)
             self._arg_cache = hit
         return hit[1], hit[2], hit[3]
 
     def query_batch_allgather_flat(self, comm, text, offsets, score_calculator, fields_boost, top_k, d_local_block,
-                                   d_all_blocks, stream=None, skip=0, match="any"):
+                                   d_all_blocks, stream=None, skip=0, match="any", filter=None):
         """ps_snapshot_query_batch_allgather_flat: score this rank's shard into d_local_block and
         all-gather every rank's block into d_all_blocks (ncclAllGather inside the library, ordered on
         `stream`).  comm: dist.Comm or None (one rank: no collective).  skip > 0 (the same on every rank): blocks of
         ranks [skip, skip + top_k), ps_snapshot_query_batch_allgather_page_flat.  match (the same on every rank): as
         query_batch."""
-        desc, b, nb = self._cached_args(score_calculator, fields_boost, match)
+        desc, b, nb = self._cached_args(score_calculator, fields_boost, match, filter)
         head = (self._h, comm._h if comm is not None else None, C.byref(desc), text.ctypes.data, offsets.ctypes.data,
                 len(offsets) - 1, b, nb, None, None)
         tail = (top_k, d_local_block, d_all_blocks, stream if stream else None)
@@ -403,12 +443,12 @@ class Snapshot:
         except PsError as e:
             _raise(e)
 
-    def plan_ahead_flat(self, text, offsets, score_calculator, fields_boost=None, match="any"):
+    def plan_ahead_flat(self, text, offsets, score_calculator, fields_boost=None, match="any", filter=None):
         """ps_snapshot_plan_ahead_flat: announce the next flat batch (its planner count pass starts now); the flat query
         call that follows with the same (text, offsets) finds the totals ready.  -> accepted (bool); never for
-        match="all", which is planned on the host."""
-        desc = (self._cached_args(score_calculator, fields_boost, match)[0] if fields_boost is not None
-                else _scorer_desc(score_calculator, match))
+        match="all" or a filter, which are planned on the host."""
+        desc = (self._cached_args(score_calculator, fields_boost, match, filter)[0] if fields_boost is not None
+                else _scorer_desc(score_calculator, match, filter=filter))
         ok = C.c_int(0)
         _lib.check(self._L.ps_snapshot_plan_ahead_flat(self._h, C.byref(desc), text.ctypes.data, offsets.ctypes.data, len(offsets) - 1,
                                                        C.byref(ok)))
