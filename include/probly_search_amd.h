@@ -187,6 +187,11 @@ uint32_t ps_abi_version(void);
  * they are created and again at the next batch after any ps_set_option.  The list (PS_EINVAL for any other name):
  *   PS_DAAT (1)  PS_DAAT_MIN_BATCH (8)  PS_DAAT_MULTI (1)  PS_DAAT_SMALL (1)  PS_DAAT_SMALL_NL (1)  PS_DAAT_SPLIT (1)  PS_DAAT_Z (1)
  *   PS_DAAT_Z_SPLIT (1)  PS_DAAT_PRIME (1)  PS_DAAT_CHUNK (4096): which exact-pruning kernels take which batches, threshold priming;
+ *   PS_DAAT_TIERS (1): k_daat_small's own stream reads score-tiered scan copies of the long lists (0: the doc-sorted originals everywhere).
+ *     The copies cost 20 bytes per posting of the tiered lists (counted in device_bytes, kept once allocated) and exist only while the
+ *     snapshot carries no delta: one removal or addition applied by ps_snapshot_update switches them off for every list until the next
+ *     full flatten.  A pipeline of batches is ~11 % faster with them, a single synchronous batch the same within its spread
+ *     (DESIGN.md section 3);
  *   PS_DEVICE_PLAN (1): the device-side planner;  PS_ROW_CACHE_MB (4096): resident dense rows;  PS_DENSE_MIN_USES (4), PS_DENSE_MAX_ROWS (64);
  *   PS_WORK_COUNTERS (1), PS_KERNEL_TIMERS (1): ps_snapshot_work_counters / ps_snapshot_kernel_breakdown instrumentation;
  *   PS_SCORE_ALT (1), PS_DCTX (5), PS_PLAN_AHEAD_DEPTH (3): scoring queues, batch contexts, announced batches;

@@ -230,7 +230,7 @@ ps_status ps_set_option(const char* name, uint32_t value) {
   // environment variable of its name, and through this call only when PS_EXPERIMENT_KNOBS=1 (tools/knob_sweep.py).
   static const char* const kRuntime[] = {
       "PS_DAAT", "PS_DAAT_MIN_BATCH", "PS_DAAT_MULTI", "PS_DAAT_SMALL", "PS_DAAT_SMALL_NL", "PS_DAAT_SPLIT", "PS_DAAT_Z", "PS_DAAT_Z_SPLIT",
-      "PS_DAAT_PRIME", "PS_DAAT_CHUNK", "PS_DEVICE_PLAN", "PS_ROW_CACHE_MB", "PS_WORK_COUNTERS", "PS_KERNEL_TIMERS", "PS_SCORE_ALT", "PS_DCTX",
+      "PS_DAAT_PRIME", "PS_DAAT_TIERS", "PS_DAAT_CHUNK", "PS_DEVICE_PLAN", "PS_ROW_CACHE_MB", "PS_WORK_COUNTERS", "PS_KERNEL_TIMERS", "PS_SCORE_ALT", "PS_DCTX",
       "PS_PLAN_AHEAD_DEPTH", "PS_RESULT_PINNED_MIN_KB", "PS_FULL_PARTS_MIN_KB", "PS_DENSE_MIN_USES", "PS_DENSE_MAX_ROWS", "PS_PLAN_THREADS",
       "PS_FLATTEN_THREADS"};
   bool known = false;

@@ -176,6 +176,8 @@ struct Tuning {
   uint32_t daat_z = 1;           // PS_DAAT_Z: zero_to_one top-k batches of simple queries with <= 4 lists take K1dz k_daat_z (ps_z21_daat.hpp)
   uint32_t daat_prime = 1;       // PS_DAAT_PRIME: threshold priming - a query's threshold starts at the K-th best posting score of its best single list (k_list_kth), lists that are non-essential under it get no work items (0: thresholds start at 0)
   uint32_t daat_sample_div = 24; // PS_DAAT_SAMPLE_DIV: multi-expansion K1d launches (k_daat<F, true>: C5) start with the chunks below doc id ~ N / this, of every rank (0: plain rank-major order)
+  uint32_t daat_tiers = 1;       // PS_DAAT_TIERS: the own stream of k_daat_small reads score-tiered scan copies of the long lists - a tier whose bound cannot reach the threshold is never read (0: the doc-sorted originals everywhere)
+  uint32_t daat_tier_min = 4096; // PS_DAAT_TIER_MIN: lists of at least this many postings get a tiered copy (experiments and tests)
   uint32_t daat_small_nl = 1;    // PS_DAAT_SMALL_NL: batches whose queries have <= 3 lists take k_daat_small<F, WC, 3> (0: always the four-list instantiation)
   uint32_t daat_split = 1;       // PS_DAAT_SPLIT: a BM25 K1d batch that holds queries k_daat_small takes AND others (more than 4 lists, several expansions of a term) is scored by both kernels, each over its part of the item array (0: one such query sends the whole batch to k_daat)
   uint32_t daat_sample_all = 0;  // PS_DAAT_SAMPLE_ALL: ... every K1d BM25 launch does (C2 / C4: slower)
@@ -261,6 +263,21 @@ struct EngineImpl {
     double last_ms = 0.0;  // host wall time of the most recent (re)computation's enqueue
     uint64_t recomputed = 0;
   } bounds;
+  // K1d score-tiered scan copies (ps_prep_kernels.hpp, k_tier_*): built behind the score plane and the priming tables they are cut
+  // from, for a snapshot state without deltas (a delta changes every plane value; with delta layers or tombstones the own
+  // streams read the originals)
+  struct Tiers {
+    bool valid = false;            // the copies match bounds.recomputed / the knobs below
+    uint64_t bounds_gen = ~0ull;
+    uint32_t min_len = 0;
+    uint32_t n_lists = 0;          // tiered lists (0: none - nothing is passed to the preparation)
+    uint64_t bytes = 0;            // device bytes of the copies, counted in EngineImpl::bytes
+    uint64_t doc_cap = 0;          // postings the doc-id array has room for (0: as created - the planes' capacity)
+    DevBuf<uint32_t> of_layer, seg_cnt;
+    DevBuf<TierList> lists;
+    DevBuf<unsigned long long> bound;
+    DevBuf<TierTables> tables;
+  } tiers;
   // K1d dense-row candidates: the densest lists of the snapshot (static slots), chosen on the host per
   // snapshot state / knobs; which of them a batch reads is decided on the device (k_prep_finish)
   struct RowCands {
@@ -1022,6 +1039,8 @@ void Tuning::load() {
     daat_sample_all = env_u32("PS_DAAT_SAMPLE_ALL", daat_sample_all);
     daat_split = env_u32("PS_DAAT_SPLIT", daat_split);
     daat_small_nl = env_u32("PS_DAAT_SMALL_NL", daat_small_nl);
+    daat_tiers = env_u32("PS_DAAT_TIERS", daat_tiers);
+    daat_tier_min = std::max(1u, env_u32("PS_DAAT_TIER_MIN", daat_tier_min));
     dctx = std::max(2u, std::min((uint32_t)N_DCTX, env_u32("PS_DCTX", dctx)));
     daat_z_d0_div = env_u32("PS_DAAT_Z_D0_DIV", daat_z_d0_div);
     daat_z_level_shift = env_u32("PS_DAAT_Z_LEVEL_SHIFT", daat_z_level_shift);
@@ -1377,6 +1396,79 @@ void ensure_row_candidates(EngineImpl& m, hipStream_t st) {
   rc.valid = true;
 }
 
+// Score-tiered scan copies of the lists of >= PS_DAAT_TIER_MIN postings (ps_prep_kernels.hpp, k_tier_*): cut from the score plane
+// and the priming tables ensure_list_bounds has just made current on `st`; rebuilt when those were recomputed.  One and two
+// fields, and only for a snapshot state without deltas - false: the batch reads the originals.
+bool ensure_tiers(EngineImpl& m, hipStream_t st) {
+  const Snapshot& s = *m.snap;
+  EngineImpl::Tiers& t = m.tiers;
+  EngineImpl::ListBounds& lb = m.bounds;
+  if (!m.tune.daat_tiers || s.F > 2 || s.n_delta_layers != 0 || s.n_ids != s.n_docs || !lb.kth.p || !lb.n_units) return false;
+  // (the priming tables only supply each list's largest key, the scale of the tier cuts; they are rebuilt with the plane whatever
+  // PS_DAAT_PRIME says.  A stale or zero value would only place the cuts badly, never make a result wrong: k_tier_count and
+  // k_tier_scatter classify with the same tier_of_key, and a tier's bound comes from the postings that are actually in it)
+  if (t.valid && t.bounds_gen == lb.recomputed && t.min_len == m.tune.daat_tier_min) return t.n_lists != 0;
+  // (the copies may still be read by the scoring kernels of batches in flight)
+  for (auto& c : m.dctx)
+    if (c.busy && c.scored) PS_HIP(hipStreamWaitEvent(st, c.scored, 0));
+  const size_t nl = s.layers.size();
+  std::vector<uint32_t> of(std::max<size_t>(nl, 1), NO_TIERS);
+  std::vector<TierList> lists;
+  uint64_t copy = 0, segs = 0;
+  for (size_t l = 0; l < nl; ++l) {
+    const uint32_t len = s.layers[l].len;
+    if (len < m.tune.daat_tier_min || (uint64_t)s.P + copy + len >= 0xFFFFFFFFull) continue;  // (DItem::begin leads into the copy: 32 bits)
+    TierList L;
+    memset(&L, 0, sizeof(L));
+    L.copy_off = copy; L.seg0 = (uint32_t)segs; L.layer = (uint32_t)l; L.len = len;
+    of[l] = (uint32_t)lists.size();
+    lists.push_back(L);
+    copy += len;
+    segs += (len + 16383u) / 16384u;
+  }
+  t.n_lists = (uint32_t)lists.size();
+  t.bounds_gen = lb.recomputed;
+  t.min_len = m.tune.daat_tier_min;
+  t.valid = true;
+  if (lists.empty()) return false;
+  t.of_layer.ensure(of.size() + 1);
+  t.lists.ensure(lists.size() + 1);
+  t.seg_cnt.ensure(segs * TIER_MAX + 1);
+  t.bound.ensure(lists.size() * TIER_MAX * TIER_BOUND_WORDS + 1);
+  t.tables.ensure(1);
+  // the copies lie behind the postings, at the same posting index in the doc-id array and in the score plane: both grow by the
+  // copies' size (nothing in flight reads the old arrays: the caller's stream has waited, and a free synchronises the device)
+  PS_HIP(hipStreamSynchronize(st));
+  if (t.doc_cap < (uint64_t)s.P + copy) {
+    uint32_t* nd = nullptr;
+    PS_HIP(hipMalloc((void**)&nd, ((size_t)s.P + copy + 1) * 4));
+    PS_HIP(hipMemcpy(nd, m.d_doc, (size_t)s.P * 4, hipMemcpyDeviceToDevice));
+    PS_HIP(hipDeviceSynchronize());
+    (void)hipFree(m.d_doc);
+    m.d_doc = nd;
+    t.doc_cap = (uint64_t)s.P + copy;
+  }
+  lb.plane.ensure_keep(((size_t)s.P + copy) * s.F + 2, (size_t)s.P * s.F);
+  // (the two arrays only grow, and what they grew by stays allocated - and counted - when later states tier fewer lists or none)
+  const uint64_t grown = copy * (4 + 8 * (uint64_t)s.F);
+  if (grown > t.bytes) { m.bytes += grown - t.bytes; t.bytes = grown; }
+  const TierTables tt{t.of_layer.p, t.lists.p, reinterpret_cast<const double*>(t.bound.p), (uint64_t)s.P};
+  PS_HIP(hipMemcpyAsync(t.tables.p, &tt, sizeof(tt), hipMemcpyHostToDevice, st));
+  PS_HIP(hipMemcpyAsync(t.of_layer.p, of.data(), of.size() * 4, hipMemcpyHostToDevice, st));
+  PS_HIP(hipMemcpyAsync(t.lists.p, lists.data(), lists.size() * sizeof(TierList), hipMemcpyHostToDevice, st));
+  PS_HIP(hipMemsetAsync(t.seg_cnt.p, 0, (segs * TIER_MAX + 1) * 4, st));
+  PS_HIP(hipMemsetAsync(t.bound.p, 0, (lists.size() * TIER_MAX * TIER_BOUND_WORDS + 1) * 8, st));
+  const dim3 grid((lb.n_units + 3) / 4), block(256);
+  if (s.F == 1) hipLaunchKernelGGL(k_tier_count<1>, grid, block, 0, st, lb.units.p, lb.n_units, m.d_layer_a.p, lb.plane.p, lb.kth.p, t.of_layer.p, t.lists.p, lb.dirs.p, t.seg_cnt.p, t.bound.p);
+  else hipLaunchKernelGGL(k_tier_count<2>, grid, block, 0, st, lb.units.p, lb.n_units, m.d_layer_a.p, lb.plane.p, lb.kth.p, t.of_layer.p, t.lists.p, lb.dirs.p, t.seg_cnt.p, t.bound.p);
+  hipLaunchKernelGGL(k_tier_scan, dim3((t.n_lists + WAVE - 1) / WAVE), dim3(WAVE), 0, st, t.lists.p, t.n_lists, t.seg_cnt.p);
+  if (s.F == 1) hipLaunchKernelGGL(k_tier_scatter<1>, grid, block, 0, st, lb.units.p, lb.n_units, m.d_layer_a.p, lb.plane.p, m.d_doc, lb.kth.p, t.of_layer.p, t.lists.p, t.seg_cnt.p, m.d_doc + s.P, lb.plane.p + (size_t)s.P * s.F);
+  else hipLaunchKernelGGL(k_tier_scatter<2>, grid, block, 0, st, lb.units.p, lb.n_units, m.d_layer_a.p, lb.plane.p, m.d_doc, lb.kth.p, t.of_layer.p, t.lists.p, t.seg_cnt.p, m.d_doc + s.P, lb.plane.p + (size_t)s.P * s.F);
+  PS_HIP(hipGetLastError());
+  PS_HIP(hipStreamSynchronize(st));  // (`of`, `lists` and `tt` are pageable and leave scope; once per snapshot state)
+  return true;
+}
+
 // A preparation kernel found the device's item counts above the ones the host sized a scoring launch from (the "which kernel takes
 // this query" rule lives in the planner's count pass, in k_plan and in k_prep_query): some batch since the last check may have
 // skipped items.  Reported at the next submission / result fetch as an internal error instead of a silently wrong top-k.
@@ -1461,9 +1553,16 @@ void launch_prep(EngineImpl& m, EngineImpl::DaatCtx& c, const ps_scorer_desc& sc
     pp.kth_rank = j;
     pp.prime_keep_items = m.tune.daat_prime == 2 ? 1u : 0u;
   }
+  // score-tiered scan copies: only where the batch's small queries (<= 4 lists, one per query term) go to k_daat_small - launch_daat's rule
+  const bool small_launch = m.tune.daat_small && !m.tune.daat_persistent && (split_kinds || (!multi && p.max_entries <= (uint32_t)DAAT_SMALL_MAX));
+  if (small_launch && ensure_tiers(m, st)) {
+    pp.tiers = m.tiers.tables.p;
+    kp.doc = m.d_doc; kp.splane = m.bounds.plane.p;  // (both may have moved when they grew)
+  }
   if (B) {
     hipLaunchKernelGGL(k_prep_query, dim3((uint32_t)((B + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, pp);
     if (ne) hipLaunchKernelGGL(k_prep_items, dim3((uint32_t)((ne + 2 * WAVE - 1) / (2 * WAVE))), dim3(2 * WAVE), 0, st, pp);
+    if (ne && pp.tiers) hipLaunchKernelGGL(k_prep_tier_items, dim3((uint32_t)((ne + 2 * WAVE - 1) / (2 * WAVE))), dim3(2 * WAVE), 0, st, pp);
     PS_HIP(hipGetLastError());
   }
   kp.dentry = c.dentry.p; kp.ditems = c.ditems.p; kp.qslot = c.qslot.p; kp.qslot_n = c.qslot_n.p;
@@ -1547,8 +1646,7 @@ size_t count_daat_items(const EngineImpl& m, const Plan& plan, uint32_t* max_slo
   uint32_t mx = 0;
   const size_t B = plan.qbeg.size() - 1;
   auto chunks = [&](uint32_t len, uint32_t div) {
-    const uint32_t c = std::max<uint32_t>(m.tune.daat_chunk, ((len + div - 1) / div + 255) & ~255u);
-    return (len + c - 1) / c;
+    return daat_items_of(len, daat_chunk_of(div, m.tune.daat_chunk, len));
   };
   for (size_t q = 0; q < B; ++q) {
     uint32_t sl = 0;

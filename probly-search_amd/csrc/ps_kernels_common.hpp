@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "../../include/probly_search_amd.h"
+#include "ps_items.hpp"
 
 namespace ps {
 
@@ -96,12 +97,17 @@ struct DItem {         // a chunk of one list
   // leave, and with these here that costs two dependent loads (item -> threshold) instead of three
   double skip_thr;
   uint32_t q;
-  uint32_t _pad;
+  uint32_t _pad;       // 1: `begin` leads into the list's score-tiered scan copy (k_prep_tier_items).  A marker for traces and
+                       // debugging only: k_daat_small needs no test of it - the copy is reached through the loads it has
 };
 
+// The first two words change meaning along the preparation chain: k_prep_query writes the query's kind and "no items" bits /
+// the list's chunks in the sample phase; k_prep_items consumes them and - only when the batch has tiered scan copies -
+// rewrites them for k_prep_tier_items as the list's ordinal / its first item (NO_TIERS: not re-addressed).  Nothing behind
+// k_prep_tier_items reads this array, and k_prep_query rewrites it whole for the next batch.
 struct DItemGen {      // per plan entry: k_prep_items expands it into its DItems on the device
-  uint32_t entry;      // plan entry
-  uint32_t item_at;    // its first item
+  uint32_t entry;      // k_prep_query: bit 0 PLAN_BIG query, bit 1 no items; behind k_prep_items (tiers): the list's ordinal
+  uint32_t item_at;    // k_prep_query: chunks in the sample phase; behind k_prep_items (tiers): its first item, or NO_TIERS
   uint32_t chunk;      // postings per item
   uint32_t first_slot; // candidate slot of its first item
 };

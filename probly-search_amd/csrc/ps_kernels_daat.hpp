@@ -997,7 +997,9 @@ __global__ __launch_bounds__(WAVE * DAAT_WGW) __attribute__((amdgpu_waves_per_eu
   const double own_eb = own.boost;
   const uint64_t own_off = own.post_off;
   const uint32_t own_rank = de.rank;
-  const double skip_thr = de.skip_thr;
+  // the ITEM's skip threshold: the list's, or - an item of a score-tiered scan copy (k_prep_tier_items; its `begin` then leads
+  // past the list into the copy, which lies behind the postings in the same doc / plane arrays) - that of the tiers it covers
+  const double skip_thr = it.skip_thr;
   // the other lists, in plan order (wave-uniform: scalar registers)
   uint64_t o_off[NO];
   uint32_t o_shift[NO], o_bm[NO], o_tbl[NO], o_row[NO], o_rank[NO];

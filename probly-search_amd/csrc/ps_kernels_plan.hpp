@@ -134,9 +134,7 @@ __device__ __forceinline__ void plan_token(const DevTrie& t, const int64_t fn, c
         e.layer = li;
         entries[w++] = e;
       } else {  // K1d work items of this list (the rule of k_prep_batch)
-        uint32_t c = ((la.z + split_div - 1) / split_div + 255u) & ~255u;
-        c = c > chunk_min ? c : chunk_min;
-        items += (la.z + c - 1) / c;
+        items += daat_items_of(la.z, daat_chunk_of(split_div, chunk_min, la.z));
       }
       postings += la.z;
       ++here;

@@ -94,6 +94,7 @@ struct PrepParams {
   uint32_t kth_rank;             // index of the smallest stored rank >= K
   unsigned long long* gthr;      // [B] the batch's threshold words: start at theta0 instead of 0
   uint32_t prime_keep_items;     // debugging (PS_DAAT_PRIME=2): thresholds are primed but every list keeps its work items
+  const struct TierTables* tiers;  // score-tiered scan copies (k_tier_*; null: off - also for every batch whose small queries do not go to k_daat_small)
   // consistency of the three copies of the "which kernel takes this query" rule (planner count pass / host, k_plan, k_prep_query):
   uint32_t host_items, host_items_big;  // what the launch grids are sized from
   uint32_t* fault;                      // engine-wide, host-mapped: {code, device items, device split, host items}; 0 = fine
@@ -244,6 +245,172 @@ __global__ __launch_bounds__(256) void k_list_kth(const BoundUnit* units, const 
       if ((uint32_t)lane + 1u == kth_rank_of(j) && top[d] > 0.0)
         atomicMax(&kth[((size_t)u.layer * D + d) * KTH_RANKS + j], (unsigned long long)__double_as_longlong(top[d]));
 }
+// ---- score-tiered scan copies ---------------------------------------------------------------------
+// A list's bound U(e) is set by its best posting; a typical posting scores a fraction of it.  Lists of at least tier_min postings
+// get a COPY of their {doc id, plane values} stably partitioned into TIER_MAX tiers by a boost-free key - the plane sum
+// (plane_0 for one field) against the list's largest: >= 0.7, >= 0.5, >= 0.35 of it, the rest - doc-sorted inside every tier,
+// with the bound inputs a list has per TIER: the per-field maxima and, for two fields, the direction supports, here in plane
+// units (idf included).  The copies lie BEHIND the postings in the doc-id array and the score plane (both grown by the copies'
+// size), at the same posting index in both, so k_daat_small reads one through the loads it has: an item's `begin` - relative to
+// its list's first posting - simply leads there (DItem::_pad = 1 marks it).  Only that kernel's own stream reads a copy; an item
+// of tier t carries skip_thr = U_t(e) + the bounds of the lists ranked below e, so a whole tier is dropped by the test that drops
+// a whole list today.  Every lookup from another list still goes through the doc-sorted originals.
+constexpr uint32_t TIER_MAX = 4;
+constexpr uint32_t TIER_BOUND_WORDS = 2 + PREP_NDIR;  // per (tiered list, tier): M_0, M_1, H_0 .. H_16
+constexpr uint32_t NO_TIERS = 0xFFFFFFFFu;
+struct TierList {  // per tiered list
+  uint64_t copy_off;             // its first posting in the copy
+  uint32_t start[TIER_MAX + 1];  // first posting of every tier within the list's copy (k_tier_scan); start[TIER_MAX] = len
+  uint32_t seg0;                 // its first 16 Ki-posting segment in the segment counters
+  uint32_t layer, len;
+};
+struct TierTables {  // in device memory: PrepParams carries one pointer (its copy on prep_query_general's frame is budgeted)
+  const uint32_t* of_layer;  // [n_layers] ordinal of the tiered list or NO_TIERS
+  const TierList* lists;     // [tiered lists]
+  const double* bound;       // [tiered lists][TIER_MAX][TIER_BOUND_WORDS], plane units
+  uint64_t base;             // posting index of the first copy (= the planes' capacity)
+};
+__device__ __forceinline__ uint32_t tier_of_key(const double key, const double top) {
+  return key >= 0.7 * top ? 0u : key >= 0.5 * top ? 1u : key >= 0.35 * top ? 2u : 3u;
+}
+template <int F_>
+__device__ __forceinline__ double tier_key(const double* plane, const uint64_t pi, double& v0, double& v1) {
+  if (F_ == 1) { v0 = plane[pi]; v1 = 0.0; return v0; }
+  const double2 t = reinterpret_cast<const double2*>(plane)[pi];
+  v0 = t.x; v1 = t.y;
+  return t.x + t.y;
+}
+// One wave per unit of k_list_bounds' work list: per tier, how many postings of the segment fall into it and the tier's bound
+// inputs (segments of a list meet through atomicMax, as in k_list_bounds).  `kth` gives the list's largest key (rank 1).
+template <int F_>
+__global__ __launch_bounds__(256) void k_tier_count(const BoundUnit* units, const uint32_t n_units, const uint4* layer_a, const double* plane,
+                                                    const unsigned long long* kth, const uint32_t* tier_of_layer, const TierList* tl,
+                                                    const double2* dirs, uint32_t* seg_cnt, unsigned long long* tb) {
+  constexpr int D = F_ == 1 ? 1 : 3;
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  if (wave >= n_units) return;
+  const BoundUnit u = units[wave];
+  const uint32_t ti = tier_of_layer[u.layer];
+  if (ti == NO_TIERS) return;
+  const uint4 la = layer_a[u.layer];
+  const uint64_t off = ((uint64_t)la.x | ((uint64_t)la.y << 32)) + u.begin;
+  const double top = __longlong_as_double((long long)kth[((size_t)u.layer * D + (D - 1)) * KTH_RANKS]);
+  const uint32_t seg = tl[ti].seg0 + u.begin / 16384u;
+  for (uint32_t t = 0; t < TIER_MAX; ++t) {  // (a pass per tier: the segment stays in L2, and a lane keeps one tier's maxima)
+    uint32_t n = 0;
+    double m0 = 0.0, m1 = 0.0, hh[PREP_NDIR];
+#pragma unroll
+    for (int d = 0; d < PREP_NDIR; ++d) hh[d] = 0.0;
+    for (uint32_t i = lane; i < u.count; i += WAVE) {
+      double v0, v1;
+      const double key = tier_key<F_>(plane, off + i, v0, v1);
+      if (tier_of_key(key, top) != t) continue;
+      ++n;
+      m0 = fmax(m0, v0); m1 = fmax(m1, v1);
+      if (F_ == 2) {
+#pragma unroll
+        for (int d = 0; d < PREP_NDIR; ++d) hh[d] = fmax(hh[d], dirs[d].x * v0 + dirs[d].y * v1);
+      }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      n += __shfl_down(n, o);
+      m0 = fmax(m0, __shfl_down(m0, o)); m1 = fmax(m1, __shfl_down(m1, o));
+    }
+    if (F_ == 2) {
+#pragma unroll
+      for (int d = 0; d < PREP_NDIR; ++d)
+        for (int o = 32; o > 0; o >>= 1) hh[d] = fmax(hh[d], __shfl_down(hh[d], o));
+    }
+    if (lane == 0) {
+      seg_cnt[(size_t)seg * TIER_MAX + t] = n;
+      unsigned long long* b = tb + ((size_t)ti * TIER_MAX + t) * TIER_BOUND_WORDS;
+      if (m0 > 0.0) atomicMax(&b[0], (unsigned long long)__double_as_longlong(m0));
+      if (m1 > 0.0) atomicMax(&b[1], (unsigned long long)__double_as_longlong(m1));
+      if (F_ == 2) {
+#pragma unroll
+        for (int d = 0; d < PREP_NDIR; ++d)
+          if (hh[d] > 0.0) atomicMax(&b[2 + d], (unsigned long long)__double_as_longlong(hh[d]));
+      }
+    }
+  }
+}
+// A thread per tiered list: the tiers' starts, and per (segment, tier) where the segment's postings of the tier go (the counts
+// are replaced by offsets within the list's copy).
+__global__ __launch_bounds__(WAVE) void k_tier_scan(TierList* tl, const uint32_t n_tl, uint32_t* seg_cnt) {
+  const uint32_t ti = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ti >= n_tl) return;
+  TierList& L = tl[ti];
+  const uint32_t n_seg = (L.len + 16383u) / 16384u;
+  uint32_t* c = seg_cnt + (size_t)L.seg0 * TIER_MAX;
+  uint32_t tot[TIER_MAX];
+  for (uint32_t t = 0; t < TIER_MAX; ++t) tot[t] = 0;
+  for (uint32_t s = 0; s < n_seg; ++s)
+    for (uint32_t t = 0; t < TIER_MAX; ++t) tot[t] += c[(size_t)s * TIER_MAX + t];
+  uint32_t at[TIER_MAX], run = 0;
+  for (uint32_t t = 0; t < TIER_MAX; ++t) { L.start[t] = run; at[t] = run; run += tot[t]; }
+  L.start[TIER_MAX] = run;  // (== len)
+  for (uint32_t s = 0; s < n_seg; ++s)
+    for (uint32_t t = 0; t < TIER_MAX; ++t) {
+      const uint32_t n = c[(size_t)s * TIER_MAX + t];
+      c[(size_t)s * TIER_MAX + t] = at[t];
+      at[t] += n;
+    }
+}
+// One wave per unit again: its postings go to their places, in order (a stable partition: doc-sorted inside every tier).
+template <int F_>
+__global__ __launch_bounds__(256) void k_tier_scatter(const BoundUnit* units, const uint32_t n_units, const uint4* layer_a, const double* plane,
+                                                      const uint32_t* doc, const unsigned long long* kth, const uint32_t* tier_of_layer,
+                                                      const TierList* tl, const uint32_t* seg_cnt, uint32_t* tdoc, double* tplane) {
+  // (tdoc / tplane: the first copy's place behind the postings of `doc` / `plane`)
+  constexpr int D = F_ == 1 ? 1 : 3;
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  if (wave >= n_units) return;
+  const BoundUnit u = units[wave];
+  const uint32_t ti = tier_of_layer[u.layer];
+  if (ti == NO_TIERS) return;
+  const uint4 la = layer_a[u.layer];
+  const uint64_t off = ((uint64_t)la.x | ((uint64_t)la.y << 32)) + u.begin;
+  const double top = __longlong_as_double((long long)kth[((size_t)u.layer * D + (D - 1)) * KTH_RANKS]);
+  const TierList L = tl[ti];
+  const uint32_t seg = L.seg0 + u.begin / 16384u;
+  uint32_t at[TIER_MAX];
+  for (uint32_t t = 0; t < TIER_MAX; ++t) at[t] = seg_cnt[(size_t)seg * TIER_MAX + t];
+  const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+  for (uint32_t i0 = 0; i0 < u.count; i0 += WAVE) {
+    const uint32_t i = i0 + (uint32_t)lane;
+    const bool on = i < u.count;
+    double v0 = 0.0, v1 = 0.0;
+    const double key = on ? tier_key<F_>(plane, off + i, v0, v1) : 0.0;
+    const uint32_t t = tier_of_key(key, top);
+    uint32_t pos = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < TIER_MAX; ++k) {
+      const unsigned long long mk = __ballot(on && t == k);
+      if (t == k) pos = at[k] + (uint32_t)__popcll(mk & lt);
+      at[k] += (uint32_t)__popcll(mk);
+    }
+    if (on && pos < L.len) {  // (pos < len always: the counts of k_tier_count come from the same keys)
+      const uint64_t o = L.copy_off + pos;
+      tdoc[o] = doc[off + i];
+      if (F_ == 1) tplane[o] = v0;
+      else reinterpret_cast<double2*>(tplane)[o] = make_double2(v0, v1);
+    }
+  }
+}
+// Upper bound of any posting score of one TIER, rounding included: prep_ub_from with bound inputs in plane units (the plane value
+// IS the readers' first operand: ((plane_x * boost_x) * eb), summed over the fields in order - every operation monotone).
+__device__ __forceinline__ double prep_tier_ub(const double* boost, const uint32_t F, const bool with_h, const double h_a, const double h_b,
+                                               const double eb, const double m0, const double m1, const double ha, const double hb) {
+  double ub_m = 0.0;
+  if (m0 > 0.0) ub_m += (m0 * boost[0]) * eb;
+  if (F == 2u && m1 > 0.0) ub_m += (m1 * boost[1]) * eb;
+  if (F != 2u || !with_h) return ub_m;
+  const double ub_j = eb * (h_a * ha + h_b * hb) * (1.0 + 1e-12) + 0x1p-1066;
+  return fmin(ub_m, ub_j);
+}
+
 // The same two numbers from values that are already in registers (one or two fields): k_prep_query requests the tables of all
 // of a query's entries together - a thread per query is a chain of dependent loads, and under a running k_daat every level of it
 // costs 3-5 us - and evaluates afterwards.  Same operations in the same order as prep_entry_ub / prep_entry_theta0.
@@ -308,8 +475,7 @@ __device__ __forceinline__ double prep_entry_ub(const PrepParams& pp, const ps_p
 }
 
 __device__ __forceinline__ uint32_t prep_chunk_of(const uint32_t split_div, const uint32_t chunk_min, const uint32_t len) {
-  const uint32_t c = ((len + split_div - 1) / split_div + 255u) & ~255u;
-  return c > chunk_min ? c : chunk_min;
+  return daat_chunk_of(split_div, chunk_min, len);  // (ps_items.hpp: the one place the rule lives)
 }
 __device__ __forceinline__ uint32_t prep_chunk(const PrepParams& pp, const uint32_t len) {
   return prep_chunk_of(pp.split_div, pp.chunk_min, len);
@@ -491,7 +657,7 @@ __device__ __forceinline__ uint32_t prep_query_small(const PrepParams& pp, const
       }
       const uint32_t c = prep_chunk(pp, len[i]);
       const bool dead = !pp.prime_keep_items && d.skip_thr < th0;  // (a list that is non-essential from the start gets no items)
-      if (!dead) slots += (len[i] + c - 1) / c;
+      if (!dead) slots += daat_items_of(len[i], c);
       ps.dead |= dead ? 1u << i : 0u;
     }
     ps.len[i] = len[i];
@@ -580,7 +746,7 @@ __device__ __noinline__ uint32_t prep_query_general(const PrepParams& pp, const 
   for (uint32_t i = 0; i < n; ++i) {
     const uint32_t len = pp.plan[b + i].len;
     const uint32_t c = prep_chunk(pp, len);
-    if (pp.prime_keep_items || !(pp.dentry[b + i].skip_thr < th0)) slots += (len + c - 1) / c;
+    if (pp.prime_keep_items || !(pp.dentry[b + i].skip_thr < th0)) slots += daat_items_of(len, c);
   }
   return slots;
 }
@@ -754,7 +920,7 @@ __global__ __launch_bounds__(WAVE) void k_prep_query(const PrepParams pp) {
         if (pp.n_cand) cd = pp.cand_of_layer[en.node];
       }
       const uint32_t c = prep_chunk(pp, len_i);
-      nc = dead ? 0u : (len_i + c - 1) / c;
+      nc = dead ? 0u : daat_items_of(len_i, c);
       ns = dead ? 0u : (big || !pp.split_kinds || pp.sample_small) ? prep_sample_chunks(pp, pp.plan[b + i], c, nc) : 0u;
       pp.gen[b + i] = DItemGen{(big ? 1u : 0u) | (dead ? 2u : 0u), ns, c, sl};  // (`entry`: gen is indexed by entry - the word carries the query's kind and "no items")
       sl += nc;
@@ -804,18 +970,20 @@ __global__ __launch_bounds__(WAVE) void k_prep_query(const PrepParams pp) {
 __global__ __launch_bounds__(2 * WAVE) void k_prep_items(const PrepParams pp) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool have = i < pp.ne;
-  uint32_t nc = 0, ns = 0, bk = 0, bs = 0, len_i = 0, chunk = 1, first_slot = 0, q_i = 0;
+  uint32_t nc = 0, ns = 0, bk = 0, bs = 0, len_i = 0, chunk = 1, first_slot = 0, q_i = 0, layer_i = 0;
   double skip_i = 0.0;
+  bool big_i = false;
   if (have) {
     ps_plan_entry& en = pp.plan[i];
     const DItemGen g = pp.gen[i];
     const uint32_t len = en.len, c = g.chunk;
-    len_i = len; chunk = c; first_slot = g.first_slot;
+    len_i = len; chunk = c; first_slot = g.first_slot; layer_i = en.node;
     const DEntry de_i = pp.dentry[i];
     const bool dead = (g.entry & 2u) != 0u;  // (k_prep_query: the list is non-essential under the query's primed threshold - no items)
-    nc = dead ? 0u : (len + c - 1) / c;
+    nc = dead ? 0u : daat_items_of(len, c);
     ns = g.item_at;  // (k_prep_query: the list's chunks in the sample phase)
     const bool big = (g.entry & 1u) != 0u;  // (... and its query's kind)
+    big_i = big;
     skip_i = de_i.skip_thr; q_i = de_i.q;
     bk = prep_bucket(de_i.rank, len, pp.multi != 0u && (big || !pp.split_kinds), big);
     bs = (big ? PREP_SET_BUCKETS : 0u) + (de_i.rank < PREP_SAMPLE_BUCKETS ? de_i.rank : PREP_SAMPLE_BUCKETS - 1u);
@@ -855,6 +1023,63 @@ __global__ __launch_bounds__(2 * WAVE) void k_prep_items(const PrepParams pp) {
       const uint32_t a = j < ns ? at_s + j : at + (j - ns);
       if (a < pp.items_cap) pp.items[a] = DItem{i, pb, min(chunk, len_i - pb), first_slot + j, skip_i, q_i, 0u};
     }
+    // for k_prep_tier_items: the list's ordinal (the entry's `node` may now name a dense row) and where its items went
+    if (pp.tiers != nullptr) {
+      pp.gen[i].entry = layer_i;
+      pp.gen[i].item_at = (nc != 0u && ns == 0u && !big_i) ? at : NO_TIERS;
+    }
+  }
+}
+
+// Score-tiered scan copies (k_tier_* above), a thread per list, behind k_prep_items: the items of a tiered list of a query
+// k_daat_small takes (<= 4 lists, one per query term) are re-addressed to the copy - chunk j covers [j * chunk, ...) of the COPY's
+// order - and each carries, instead of the list's skip threshold, (U_t + the bounds of the lists ranked below) * slack for the
+// tiers t it touches: the largest of them (tiers are ordered by a boost-free key, so under unequal boosts a lower tier may have
+// the higher bound), never more than the list's own.  Nothing else about the items changes: same count, same slots.
+__global__ __launch_bounds__(2 * WAVE) void k_prep_tier_items(const PrepParams pp) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= pp.ne) return;
+  const DItemGen g = pp.gen[i];
+  if (g.item_at == NO_TIERS) return;
+  const TierTables tt = *pp.tiers;
+  const uint32_t ti = tt.of_layer[g.entry];
+  if (ti == NO_TIERS) return;
+  const DEntry de = pp.dentry[i];
+  const uint32_t b = pp.qbeg[de.q], n = pp.qbeg[de.q + 1] - b;
+  if (n > 4u) return;
+  // what the lists ranked below can add, summed in plan order as the skip threshold's terms are; one list per query term only
+  double below = 0.0;
+  for (uint32_t j = 0; j < n; ++j) {
+    if (j && pp.plan[b + j].qterm == pp.plan[b + j - 1].qterm) return;
+    const DEntry dj = pp.dentry[b + j];
+    if (dj.rank > de.rank) below += dj.ub;
+  }
+  const TierList L = tt.lists[ti];
+  const bool with_h = pp.F == 2u && pp.bound_h != nullptr;
+  const double eb = pp.plan[i].boost;
+  const uint64_t rel = tt.base + L.copy_off - pp.plan[i].post_off;  // (the planes' capacity is not below any list's first posting)
+  double tier_skip[TIER_MAX];
+  for (uint32_t t = 0; t < TIER_MAX; ++t) {
+    const double* tb = tt.bound + ((size_t)ti * TIER_MAX + t) * TIER_BOUND_WORDS;
+    const double ub_t = prep_tier_ub(pp.boost, pp.F, with_h, pp.h_a, pp.h_b, eb, tb[0], tb[1], with_h ? tb[2 + pp.h_lo] : 0.0,
+                                     with_h ? tb[3 + pp.h_lo] : 0.0);
+    double sk = (ub_t + below) * PREP_SLACK;
+    if (!(sk >= 0.0)) sk = INFINITY;
+    tier_skip[t] = fmin(sk, de.skip_thr);  // (the list's own threshold holds for every tier)
+  }
+  const uint32_t nc = daat_items_of(L.len, g.chunk);
+  for (uint32_t j = 0; j < nc; ++j) {
+    const uint32_t a = g.item_at + j;
+    if (a >= pp.items_cap) break;
+    const uint32_t pb = j * g.chunk, cnt = min(g.chunk, L.len - pb);
+    double sk = 0.0;
+    for (uint32_t t = 0; t < TIER_MAX; ++t)
+      if (L.start[t] < pb + cnt && L.start[t + 1] > pb) sk = fmax(sk, tier_skip[t]);
+    if (!(sk > 0.0)) sk = de.skip_thr;
+    DItem& it = pp.items[a];
+    it.begin = (uint32_t)rel + pb;
+    it.skip_thr = sk;
+    it._pad = 1u;
   }
 }
 

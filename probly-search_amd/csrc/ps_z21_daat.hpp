@@ -205,7 +205,7 @@ __global__ __launch_bounds__(WAVE) void k_zprep_query(const ZPrepParams pp) {
       d.q = q;
       pp.dentry[b + i] = d;
       const uint32_t c = prep_chunk_of(pp.split_div, pp.chunk_min, len[i]);
-      slots += (len[i] + c - 1) / c;
+      slots += daat_items_of(len[i], c);
     }
   }
   const uint32_t s0 = wave_add_by_key(&pp.ctl->total_slots, 0u, slots, have && n != 0);
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(WAVE) void k_zprep_query(const ZPrepParams pp) {
     if (on) {
       const ps_plan_entry& en = pp.plan[b + i];
       const uint32_t c = prep_chunk_of(pp.split_div, pp.chunk_min, en.len);
-      nc = (en.len + c - 1) / c;
+      nc = daat_items_of(en.len, c);
       len_i = en.len;
       const uint32_t sh = en.shift & 0xFFu;
       uint32_t prev = 0;
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(2 * WAVE) void k_zprep_items(const ZPrepParams pp) 
     const ps_plan_entry& en = pp.plan[i];
     const DItemGen g = pp.gen[i];
     len = en.len; chunk = g.chunk; first_slot = g.first_slot;
-    nc = (len + chunk - 1) / chunk;
+    nc = daat_items_of(len, chunk);
 #pragma unroll
     for (int l = 0; l < Z_LEVELS; ++l) {
       nb[l] = pp.nbelow[(size_t)i * Z_LEVELS + l];
