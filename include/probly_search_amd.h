@@ -180,8 +180,10 @@ int ps_device_count(void);
  * 8: the match-count entry points (ps_snapshot_count_batch, ps_snapshot_count_batch_device_flat).
  * 9: ps_work_counters.run_results (thresholded stage 1 of deep top-k and result pages).
  * 10: ps_scorer_desc.match_mode (was _pad; PS_MATCH_ALL: conjunctive queries).
- * 11: ps_scorer_desc.filter (trailing field), ps_snapshot_filter_new / ps_filter_free / ps_filter_len. */
-#define PS_ABI_VERSION 11u
+ * 11: ps_scorer_desc.filter (trailing field), ps_snapshot_filter_new / ps_filter_free / ps_filter_len.
+ * 12: facet counts (ps_snapshot_facet_new / ps_facet_free / ps_facet_values / ps_facet_len,
+ *     ps_snapshot_facet_counts_batch, ps_snapshot_facet_counts_batch_device_flat); no struct changes. */
+#define PS_ABI_VERSION 12u
 uint32_t ps_abi_version(void);
 /* Run-time options by name.  A value set here wins over the environment variable of the same name; engines read their options when
  * they are created and again at the next batch after any ps_set_option.  The list (PS_EINVAL for any other name):
@@ -451,6 +453,44 @@ ps_status ps_snapshot_count_batch_device_flat(ps_snapshot* snap, const ps_scorer
 ps_status ps_snapshot_filter_new(ps_snapshot* snap, const uint64_t* keys, size_t n_keys, ps_filter** out);
 void ps_filter_free(ps_filter* f);
 uint64_t ps_filter_len(const ps_filter* f);
+
+/* Facet counts - the sidebar beside the page and the total, "Books 12 031 - Music 877 - Games 45": how the matches of a
+ * query spread over the values of a per-document attribute.  A ps_facet is one value id per document, resolved once on
+ * the snapshot's device: keys[i] carries values[i] < n_values - any order, keys the snapshot does not hold are ignored,
+ * a document whose key is not listed has no value and is counted nowhere, a key listed more than once takes the LARGEST
+ * of its values; n = 0 (keys and values may then be NULL) is a valid facet that counts nothing.  One copy up each,
+ * k_facet_build (a binary search per key in the doc-id -> key plane, an atomic max of value + 1, the result narrowed
+ * into a 16-bit column), one word down (the length).  PS_EINVAL: null snap / out, keys or values with n > 0,
+ * n_values = 0, a value >= n_values (checked on the host before any device work); PS_EUNSUPPORTED: n_values >
+ * PS_MAX_FACET_VALUES; PS_ENODEVICE: a host-only snapshot.  ps_facet_values: n_values.  ps_facet_len: the alive documents
+ * of the snapshot that carry a value.  ps_facet_free: NULL is fine; a facet may outlive its snapshot (it is then of no
+ * use).  Like a filter, a facet belongs to the snapshot AND the state it was made from: on another snapshot, or after a
+ * ps_snapshot_update that changed the snapshot (mode != 0), a call that names it is PS_EINVAL - create it again. */
+typedef struct ps_facet ps_facet;
+#define PS_MAX_FACET_VALUES 8192
+ps_status ps_snapshot_facet_new(ps_snapshot* snap, const uint64_t* keys, const uint32_t* values, size_t n, uint32_t n_values,
+                                ps_facet** out);
+void ps_facet_free(ps_facet* f);
+uint32_t ps_facet_values(const ps_facet* f);
+uint64_t ps_facet_len(const ps_facet* f);
+/* counts[q * n_values + v] = the number of documents in query q's full result list - what
+ * ps_snapshot_query_batch(top_k = 0) returns for the same descriptor, boosts and tokenizer - whose facet value is v;
+ * u64[n_queries * n_values] on the host, written whole (no need to clear it).  One launch answers every value of every
+ * query: k_facet_counts builds k_count_matches' bitset of matching documents per (query, document window) in LDS, looks
+ * the set bits up in the value column and histograms them in LDS; the settings ps_snapshot_count_batch counts by its
+ * slow route (PS_MATCH_ALL, a negative boost, bm25_k1 < 0, bm25_b outside [0, 1] ...) histogram the runs of the deep
+ * path's stage 1 instead (k_facet_runs): slower, the same exact numbers.  The descriptor is honoured as the count calls
+ * honour it (match_mode, filter, both built-in scorers); statuses as ps_snapshot_count_batch, and PS_EINVAL for a null
+ * facet or counts and for a facet of another snapshot or snapshot state.  Host-planned. */
+ps_status ps_snapshot_facet_counts_batch(ps_snapshot* snap, const ps_scorer_desc* scorer, const ps_str* queries, size_t n_queries,
+                                         const double* fields_boost, size_t n_boost, ps_tokenizer_fn tokenizer, void* user,
+                                         const ps_facet* facet, uint64_t* counts);
+/* The same counts into d_counts, u64[n_queries * n_values] on the snapshot's device, written whole.  text / offsets and
+ * the semantics of `hip_stream` are those of ps_snapshot_count_batch_device_flat. */
+ps_status ps_snapshot_facet_counts_batch_device_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const char* text,
+                                                     const uint64_t* offsets, size_t n_queries, const double* fields_boost,
+                                                     size_t n_boost, ps_tokenizer_fn tokenizer, void* user, const ps_facet* facet,
+                                                     void* d_counts, void* hip_stream);
 
 /* ---- multi-GPU: replicated corpus, query batch sharded across ranks, RCCL all-gather of top-k ----
  * Queries are independent (each Index::query owns its scores / visited maps, src/query.rs:31,37),

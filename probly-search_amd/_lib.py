@@ -18,7 +18,7 @@ class PsError(RuntimeError):
 
 PS_OK, PS_EINVAL, PS_ENOMEM, PS_EHIP, PS_EUNSUPPORTED, PS_ENODEVICE, PS_ERCCL = range(7)
 PS_COMM_ID_BYTES = 128
-PS_ABI_VERSION = 11  # include/probly_search_amd.h
+PS_ABI_VERSION = 12  # include/probly_search_amd.h
 
 
 class Str(C.Structure):
@@ -180,6 +180,14 @@ SYMBOLS = {
     "ps_snapshot_filter_new": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(_P)]),
     "ps_filter_free": (None, [_P]),
     "ps_filter_len": (C.c_uint64, [_P]),
+    "ps_snapshot_facet_new": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, C.POINTER(_P)]),
+    "ps_facet_free": (None, [_P]),
+    "ps_facet_values": (C.c_uint32, [_P]),
+    "ps_facet_len": (C.c_uint64, [_P]),
+    "ps_snapshot_facet_counts_batch": (C.c_int, [_P, C.POINTER(ScorerDesc), C.POINTER(Str), C.c_size_t, C.POINTER(C.c_double),
+                                                 C.c_size_t, _P, _P, _P, _P]),
+    "ps_snapshot_facet_counts_batch_device_flat": (C.c_int, [_P, C.POINTER(ScorerDesc), _P, _P, C.c_size_t,
+                                                             C.POINTER(C.c_double), C.c_size_t, _P, _P, _P, _P, _P]),
     "ps_snapshot_query_batch_device_planned_flat": (C.c_int, [_P, C.POINTER(ScorerDesc), _P, _P, C.c_size_t,
                                                               C.POINTER(C.c_double), C.c_size_t, C.c_size_t, _P, _P,
                                                               _P, _P]),

@@ -722,6 +722,64 @@ ps_status ps_snapshot_filter_new(ps_snapshot* snap, const uint64_t* keys, size_t
 void ps_filter_free(ps_filter* f) { ps::filter_free(f); }
 uint64_t ps_filter_len(const ps_filter* f) { return f ? f->len : 0; }
 
+// Both facet-count entry points: run_count's shape with Engine::run_facet_counts behind it.
+static ps_status run_facet_counts(ps_snapshot* snap, const ps_scorer_desc* scorer, const std::vector<std::string_view>& qs,
+                                  const double* fields_boost, size_t n_boost, ps_tokenizer_fn tokenizer, void* user, const ps_facet* facet,
+                                  void* d_counts, uint64_t* h_counts, void* hip_stream) {
+  ps_status st = check_query_args(snap, scorer, fields_boost, n_boost);
+  if (st != PS_OK) return st;
+  if (!facet || (!d_counts && !h_counts)) return fail(PS_EINVAL, "null argument");
+  const double t0 = wall_ms();
+  ps::Plan plan;
+  plan_batch(snap, *scorer, qs, tokenizer, user, plan);
+  const double t1 = wall_ms();
+  ps_batch_stats stats;
+  snap->engine->run_facet_counts(*scorer, fields_boost, plan, *facet, d_counts, h_counts, hip_stream, stats);
+  stats.plan_ms = t1 - t0;
+  stats.total_ms = wall_ms() - t0;
+  set_stats(snap, stats);
+  return PS_OK;
+}
+
+ps_status ps_snapshot_facet_counts_batch(ps_snapshot* snap, const ps_scorer_desc* scorer, const ps_str* queries, size_t n_queries,
+                                         const double* fields_boost, size_t n_boost, ps_tokenizer_fn tokenizer, void* user,
+                                         const ps_facet* facet, uint64_t* counts) {
+  return guard([&]() -> ps_status {
+    if (n_queries && !queries) return fail(PS_EINVAL, "null argument");
+    return run_facet_counts(snap, scorer, views_of(queries, n_queries), fields_boost, n_boost, tokenizer, user, facet, nullptr, counts, nullptr);
+  });
+}
+
+ps_status ps_snapshot_facet_counts_batch_device_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const char* text,
+                                                     const uint64_t* offsets, size_t n_queries, const double* fields_boost,
+                                                     size_t n_boost, ps_tokenizer_fn tokenizer, void* user, const ps_facet* facet,
+                                                     void* d_counts, void* hip_stream) {
+  return guard([&]() -> ps_status {
+    if (n_queries && (!text || !offsets)) return fail(PS_EINVAL, "null argument");
+    std::vector<std::string_view> qs(n_queries);
+    for (size_t i = 0; i < n_queries; ++i) qs[i] = std::string_view(text + offsets[i], (size_t)(offsets[i + 1] - offsets[i]));
+    return run_facet_counts(snap, scorer, qs, fields_boost, n_boost, tokenizer, user, facet, d_counts, nullptr, hip_stream);
+  });
+}
+
+ps_status ps_snapshot_facet_new(ps_snapshot* snap, const uint64_t* keys, const uint32_t* values, size_t n, uint32_t n_values,
+                                ps_facet** out) {
+  return guard([&]() -> ps_status {
+    if (!snap || !out || (n && (!keys || !values))) return fail(PS_EINVAL, "null argument");
+    if (!n_values) return fail(PS_EINVAL, "a facet needs at least one value (n_values = 0)");
+    if (n_values > PS_MAX_FACET_VALUES) return fail(PS_EUNSUPPORTED, "more than PS_MAX_FACET_VALUES (8192) facet values");
+    for (size_t i = 0; i < n; ++i)
+      if (values[i] >= n_values) return fail(PS_EINVAL, "a facet value is not below n_values");
+    if (!snap->engine) return fail(PS_ENODEVICE, "host-only snapshot: a facet is resolved on the snapshot's device");
+    *out = snap->engine->facet_new(keys, values, n, n_values);
+    return PS_OK;
+  });
+}
+
+void ps_facet_free(ps_facet* f) { ps::facet_free(f); }
+uint32_t ps_facet_values(const ps_facet* f) { return f ? f->n_values : 0; }
+uint64_t ps_facet_len(const ps_facet* f) { return f ? f->len : 0; }
+
 ps_status ps_snapshot_query_batch_device_planned_flat(ps_snapshot* snap, const ps_scorer_desc* scorer, const char* text,
                                                       const uint64_t* offsets, size_t n_queries, const double* fields_boost,
                                                       size_t n_boost, size_t top_k, void* d_keys, void* d_scores,

@@ -188,6 +188,7 @@ struct Tuning {
   uint32_t count_window_log2 = 0;  // PS_COUNT_WINDOW_LOG2: documents per window of Kc k_count_matches (0: count_window_log2's rule; 8..19)
   uint32_t conj_chunk = CONJ_CHUNK;  // PS_CONJ_CHUNK: driver postings per work item of Kj k_conj (1..CONJ_NT, one per lane)
   uint32_t conj_lists = CONJ_LISTS;  // PS_CONJ_LISTS: plan entries whose sub-ranges Kj k_conj keeps in LDS at a time (1..CONJ_LISTS)
+  uint32_t facet_replicas = 0;     // PS_FACET_REPLICAS: at most this many histogram replicas in Kh k_facet_counts / Kr k_facet_runs (0: as many as facet_replicas' rule fits; 1: the unreplicated A/B leg)
   uint32_t filter_chunk = FILTER_CHUNK;  // PS_FILTER_CHUNK: filter documents per work item of Kf k_filter_score (1..CONJ_NT, one per lane)
   uint32_t filter_drive = 2;       // PS_FILTER_DRIVE: which stage 1 a filtered BM25 slice takes (0: the lists drive, under the allow bitmap; 1: the filter drives, Kf k_filter_score; else THE DRIVER RULE of score_into_runs)
   uint32_t deep_sample_runs = 0;   // PS_DEEP_SAMPLE_RUNS: runs of a deep / paged stage 1 scored in front of k_deep_threshold (0: deep_sample_runs' rule; n: exactly n, at most n_super - 1; 0xFFFFFFFF: never threshold)
@@ -824,6 +825,62 @@ void filter_free(ps_filter* f) {
   delete f;
 }
 
+// k_facet_build (ps_kernels_facet.hpp): keys and values up in one copy each, assign (atomic max of value + 1 into a
+// zeroed 32-bit buffer) -> narrow (the 16-bit column, the alive documents with a value counted) on the engine's stream,
+// the length down.  The column covers whole words of the alive bitmap.
+ps_facet* Engine::facet_new(const uint64_t* keys, const uint32_t* values, size_t n, uint32_t n_values) {
+  EngineImpl& m = *impl_;
+  const Snapshot& s = *m.snap;
+  std::lock_guard<std::mutex> lock(m.mu);
+  PS_HIP(hipSetDevice(m.device));
+  const uint32_t n_docs = (uint32_t)s.alive.size() * 32u;
+  std::unique_ptr<ps_facet, void (*)(ps_facet*)> f(new ps_facet(), &facet_free);
+  f->state = m.state;
+  f->device = m.device;
+  f->n_values = n_values;
+  PS_HIP(hipMalloc((void**)&f->d_col, std::max<size_t>(1, n_docs) * 2));
+  PS_HIP(hipMemsetAsync(f->d_col, 0, std::max<size_t>(1, n_docs) * 2, m.stream));
+  if (n && n_docs) {
+    uint64_t* d_keys = nullptr;
+    uint32_t *d_values = nullptr, *d_build = nullptr;  // d_build: [n_docs] | the length (u64, 8-byte aligned: n_docs is even)
+    unsigned long long len = 0;
+    hipError_t e = hipMalloc((void**)&d_keys, n * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_values, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_build, ((size_t)n_docs + 2) * 4);
+    if (e == hipSuccess) e = hipMemsetAsync(d_build, 0, ((size_t)n_docs + 2) * 4, m.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_keys, keys, n * 8, hipMemcpyHostToDevice, m.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_values, values, n * 4, hipMemcpyHostToDevice, m.stream);
+    if (e == hipSuccess) {
+      unsigned long long* d_len = reinterpret_cast<unsigned long long*>(d_build + n_docs);
+      const uint32_t grid = (uint32_t)std::min<uint64_t>((n + FACET_NT - 1) / FACET_NT, 65536);
+      hipLaunchKernelGGL(k_facet_assign, dim3(grid), dim3(FACET_NT), 0, m.stream, d_keys, d_values, (uint64_t)n, m.d_keys, (uint32_t)s.n_ids, d_build);
+      hipLaunchKernelGGL(k_facet_narrow, dim3((n_docs + FACET_NT - 1) / FACET_NT), dim3(FACET_NT), 0, m.stream, d_build, m.d_alive, n_docs, f->d_col, d_len);
+      e = hipGetLastError();
+      if (e == hipSuccess) e = hipMemcpyAsync(&len, d_len, 8, hipMemcpyDeviceToHost, m.stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(m.stream);
+    (void)hipFree(d_keys);
+    (void)hipFree(d_values);
+    (void)hipFree(d_build);
+    PS_HIP(e);
+    PS_HIP(e2);
+    f->len = len;
+  } else {
+    PS_HIP(hipStreamSynchronize(m.stream));
+  }
+  return f.release();
+}
+
+void facet_free(ps_facet* f) {
+  if (!f) return;
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  if (f->device >= 0) (void)hipSetDevice(f->device);
+  if (f->d_col) (void)hipFree(f->d_col);
+  if (cur >= 0) (void)hipSetDevice(cur);
+  delete f;
+}
+
 uint64_t Engine::device_bytes() const { return impl_->bytes; }
 void Engine::kernel_times(ps_kernel_times& out, bool reset) {
   EngineImpl& m = *impl_;
@@ -1053,6 +1110,7 @@ void Tuning::load() {
     conj_lists = std::max(1u, std::min(CONJ_LISTS, env_u32("PS_CONJ_LISTS", conj_lists)));
     filter_chunk = std::max(1u, std::min((uint32_t)CONJ_NT, env_u32("PS_FILTER_CHUNK", filter_chunk)));
     filter_drive = env_u32("PS_FILTER_DRIVE", filter_drive);
+    facet_replicas = env_u32("PS_FACET_REPLICAS", facet_replicas);
 }
 
 namespace {
@@ -3258,8 +3316,10 @@ void score_into_runs(EngineImpl& m, const ps_scorer_desc& sc, const double* boos
 // of every run; everything in front of the select is the same.
 // count_totals != nullptr (enqueue_count's slow route): stage 1 alone - every slice's full_cnt is widened into
 // count_totals[row] before the next slice clears it, and no select is launched.
+// facet != nullptr (enqueue_facet_counts' slow route; count_totals is then counts, u64[B * n_values], cleared here):
+// Kr k_facet_runs histograms every slice's runs into its rows instead, one item per FACET_RUN_SLICE documents of room.
 void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, size_t skip, size_t top_k,
-                  const OutBlock& out, hipStream_t st, unsigned long long* count_totals = nullptr) {
+                  const OutBlock& out, hipStream_t st, unsigned long long* count_totals = nullptr, const ps_facet* facet = nullptr) {
   const size_t B = plan.qbeg.size() - 1;
   refresh_tuning(m);
   drop_ahead(m);
@@ -3280,8 +3340,11 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
     qa = qb;
   }
   for (size_t q = 0; q < B; ++q) max_run = std::max(max_run, cap[q + 1] - cap[q]);
+  const uint64_t facet_slices = std::max<uint64_t>(1, (max_run + FACET_RUN_SLICE - 1) / FACET_RUN_SLICE);
+  if (facet && max_q * facet_slices >= 0x7FFFFFF0ull) throw std::length_error("facet batch too large for one launch");
   join_tail(m, st);
   ensure_runs(m, max_cap, max_q);
+  if (facet) PS_HIP(hipMemsetAsync(count_totals, 0, B * facet->n_values * 8, st));
   const bool spills = !count_totals && max_run > (uint64_t)DEEP_CAND;  // only a run longer than the LDS candidate buffer can need the scratch
   if (spills) {
     m.d_sort_doc.ensure(max_cap + 1);
@@ -3294,6 +3357,15 @@ void enqueue_deep(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts,
     const Plan part = whole ? Plan() : sub_plan(plan, qa, qb);
     // only ranks [0, skip + top_k) are wanted: stage 1 may drop what cannot reach them (the count route wants every match)
     score_into_runs(m, sc, boosts, whole ? plan : part, st, count_totals ? 0u : (uint32_t)(skip + top_k));  // (check_page: below 2^32)
+    if (facet) {
+      uint32_t replicas = facet_replicas(FACET_LDS / 2, facet->n_values);  // (half the budget: no bitset beside it, 256 threads to add)
+      while (m.tune.facet_replicas && replicas > m.tune.facet_replicas) replicas >>= 1;
+      const FacetRunParams rp{m.d_full_doc.p, m.d_full_off.p, m.d_full_cnt.p, (uint32_t)facet_slices, (uint32_t)qa, (uint32_t)m.snap->n_ids};
+      const FacetParams fp{facet->d_col, count_totals, facet->n_values, (uint32_t)__builtin_ctz(replicas)};
+      hipLaunchKernelGGL(k_facet_runs, dim3((uint32_t)(nq * facet_slices)), dim3(FACET_NT), (size_t)replicas * facet->n_values * 4, st, rp, fp);
+      PS_HIP(hipGetLastError());
+      continue;
+    }
     if (count_totals) {
       hipLaunchKernelGGL(k_count_copy, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, st, m.d_full_cnt.p, count_totals + qa, (uint32_t)nq);
       PS_HIP(hipGetLastError());
@@ -3355,22 +3427,9 @@ CountRoute count_route(const Snapshot& s, const ps_scorer_desc& sc, const double
 // by a preparation kernel: the plan is on the host already (two plane reads per list), the item count sizes the grid,
 // and a kernel would have to hand that count back before the launch.  Lists, qbeg and items go up in one copy from a
 // pinned slot; totals is cleared on the stream; one launch.  Slow route: stage 1 of the deep path (enqueue_deep).
-void enqueue_count(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, unsigned long long* d_totals,
-                   hipStream_t st) {
-  const Snapshot& s = *m.snap;
-  const size_t B = plan.qbeg.size() - 1, ne = plan.entries.size();
-  refresh_tuning(m);
-  if (!B) return;
-  uint32_t pos_fields = 0;
-  const CountRoute route = count_route(s, sc, boosts, &pos_fields);
-  if (route == COUNT_SLOW) {
-    enqueue_deep(m, sc, boosts, plan, 0, 1, OutBlock{}, st, d_totals);
-    return;
-  }
-  drop_ahead(m);
-  m.last_bounds_recomputed = false;
-  m.last_kt = nullptr;
-  const uint32_t w_log2 = count_window_log2(s.n_ids, B, (uint32_t)m.n_cu, m.tune.count_window_log2);
+// (the two steps below are shared with enqueue_facet_counts, whose items and first kernel half are the same)
+std::vector<CountItem> count_items(const Snapshot& s, const Plan& plan, uint32_t w_log2) {
+  const size_t B = plan.qbeg.size() - 1;
   std::vector<CountItem> items;
   for (size_t q = 0; q < B; ++q) {
     uint32_t lo = 0xFFFFFFFFu, hi = 0;
@@ -3384,37 +3443,103 @@ void enqueue_count(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts
     for (uint32_t w = lo >> w_log2; w <= hi >> w_log2; ++w) items.push_back(CountItem{(uint32_t)q, w});
   }
   if (items.size() >= 0x7FFFFFF0ull) throw std::length_error("count batch too large for one launch");
+  return items;
+}
+// Lists, qbeg and items up in one copy from a pinned slot -> the kernel's parameters, all but where the sums go.
+CountParams stage_count(EngineImpl& m, const ps_scorer_desc& sc, const Plan& plan, const std::vector<CountItem>& items, uint32_t w_log2,
+                        uint32_t pos_fields, hipStream_t st) {
+  const Snapshot& s = *m.snap;
+  const size_t B = plan.qbeg.size() - 1, ne = plan.entries.size();
+  const size_t off_q = ne * sizeof(CountList), off_i = (off_q + (B + 1) * 4 + 15) & ~(size_t)15, total = off_i + items.size() * sizeof(CountItem);
+  Stage& sg = claim_stage(m);
+  sg.ensure(total + 16);
+  CountList* hl = reinterpret_cast<CountList*>(sg.p);
+  for (size_t e = 0; e < ne; ++e) hl[e] = CountList{plan.entries[e].post_off, plan.entries[e].len, 0u};
+  memcpy(sg.p + off_q, plan.qbeg.data(), (B + 1) * 4);
+  memcpy(sg.p + off_i, items.data(), items.size() * sizeof(CountItem));
+  m.d_count.ensure(total + 16);
+  PS_HIP(hipMemcpyAsync(m.d_count.p, sg.p, total, hipMemcpyHostToDevice, st));
+  fence_stage(sg, st);
+  CountParams cp{};
+  cp.doc = m.d_doc;
+  cp.tf = m.d_tf;
+  cp.alive = emit_bitmap(m, sc);
+  cp.lists = reinterpret_cast<const CountList*>(m.d_count.p);
+  cp.qbeg = reinterpret_cast<const uint32_t*>(m.d_count.p + off_q);
+  cp.items = reinterpret_cast<const CountItem*>(m.d_count.p + off_i);
+  cp.P = s.P;
+  cp.n_ids = (uint32_t)s.n_ids;
+  cp.w_log2 = w_log2;
+  cp.F = s.F;
+  cp.pos_fields = pos_fields;
+  return cp;
+}
+
+void enqueue_count(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, unsigned long long* d_totals,
+                   hipStream_t st) {
+  const Snapshot& s = *m.snap;
+  const size_t B = plan.qbeg.size() - 1;
+  refresh_tuning(m);
+  if (!B) return;
+  uint32_t pos_fields = 0;
+  const CountRoute route = count_route(s, sc, boosts, &pos_fields);
+  if (route == COUNT_SLOW) {
+    enqueue_deep(m, sc, boosts, plan, 0, 1, OutBlock{}, st, d_totals);
+    return;
+  }
+  drop_ahead(m);
+  m.last_bounds_recomputed = false;
+  m.last_kt = nullptr;
+  const uint32_t w_log2 = count_window_log2(s.n_ids, B, (uint32_t)m.n_cu, m.tune.count_window_log2);
+  const std::vector<CountItem> items = count_items(s, plan, w_log2);
   join_tail(m, st);
   PS_HIP(hipMemsetAsync(d_totals, 0, B * 8, st));
   if (!items.empty()) {
-    const size_t off_q = ne * sizeof(CountList), off_i = (off_q + (B + 1) * 4 + 15) & ~(size_t)15, total = off_i + items.size() * sizeof(CountItem);
-    Stage& sg = claim_stage(m);
-    sg.ensure(total + 16);
-    CountList* hl = reinterpret_cast<CountList*>(sg.p);
-    for (size_t e = 0; e < ne; ++e) hl[e] = CountList{plan.entries[e].post_off, plan.entries[e].len, 0u};
-    memcpy(sg.p + off_q, plan.qbeg.data(), (B + 1) * 4);
-    memcpy(sg.p + off_i, items.data(), items.size() * sizeof(CountItem));
-    m.d_count.ensure(total + 16);
-    PS_HIP(hipMemcpyAsync(m.d_count.p, sg.p, total, hipMemcpyHostToDevice, st));
-    fence_stage(sg, st);
-    CountParams cp{};
-    cp.doc = m.d_doc;
-    cp.tf = m.d_tf;
-    cp.alive = emit_bitmap(m, sc);
-    cp.lists = reinterpret_cast<const CountList*>(m.d_count.p);
-    cp.qbeg = reinterpret_cast<const uint32_t*>(m.d_count.p + off_q);
-    cp.items = reinterpret_cast<const CountItem*>(m.d_count.p + off_i);
+    CountParams cp = stage_count(m, sc, plan, items, w_log2, pos_fields, st);
     cp.totals = d_totals;
-    cp.P = s.P;
-    cp.n_ids = (uint32_t)s.n_ids;
-    cp.w_log2 = w_log2;
-    cp.F = s.F;
-    cp.pos_fields = pos_fields;
     const size_t lds = count_lds_bytes(w_log2);
     const void* fn = route == COUNT_FAST_ZB ? reinterpret_cast<const void*>(&k_count_matches<true>) : reinterpret_cast<const void*>(&k_count_matches<false>);
     if (lds >= 60 * 1024) PS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  // (with the static words: past 64 KiB)
     if (route == COUNT_FAST_ZB) hipLaunchKernelGGL(k_count_matches<true>, dim3((uint32_t)items.size()), dim3(COUNT_NT), lds, st, cp);
     else hipLaunchKernelGGL(k_count_matches<false>, dim3((uint32_t)items.size()), dim3(COUNT_NT), lds, st, cp);
+    PS_HIP(hipGetLastError());
+  }
+  publish_tail(m, st);
+}
+
+// Facet counts of a planned batch into d_counts (u64[B * n_values], device), all device work ordered on `st`:
+// enqueue_count with another second half.  Fast route: the same items under facet_window_log2's window, the same copy
+// from a pinned slot; counts is cleared on the stream; one launch of Kh k_facet_counts, its histogram replicated as often
+// as fits behind the bitset.  Slow route: stage 1 of the deep path, Kr k_facet_runs over every slice's runs (enqueue_deep).
+void enqueue_facet_counts(EngineImpl& m, const ps_scorer_desc& sc, const double* boosts, const Plan& plan, const ps_facet& facet,
+                          unsigned long long* d_counts, hipStream_t st) {
+  const Snapshot& s = *m.snap;
+  const size_t B = plan.qbeg.size() - 1;
+  refresh_tuning(m);
+  if (!B) return;
+  uint32_t pos_fields = 0;
+  const CountRoute route = count_route(s, sc, boosts, &pos_fields);
+  if (route == COUNT_SLOW) {
+    enqueue_deep(m, sc, boosts, plan, 0, 1, OutBlock{}, st, d_counts, &facet);
+    return;
+  }
+  drop_ahead(m);
+  m.last_bounds_recomputed = false;
+  m.last_kt = nullptr;
+  const uint32_t w_log2 = facet_window_log2(s.n_ids, B, (uint32_t)m.n_cu, m.tune.count_window_log2, facet.n_values);
+  const std::vector<CountItem> items = count_items(s, plan, w_log2);
+  join_tail(m, st);
+  PS_HIP(hipMemsetAsync(d_counts, 0, B * facet.n_values * 8, st));
+  if (!items.empty()) {
+    CountParams cp = stage_count(m, sc, plan, items, w_log2, pos_fields, st);
+    uint32_t replicas = facet_replicas(count_lds_bytes(w_log2), facet.n_values);
+    while (m.tune.facet_replicas && replicas > m.tune.facet_replicas) replicas >>= 1;
+    const FacetParams fp{facet.d_col, d_counts, facet.n_values, (uint32_t)__builtin_ctz(replicas)};
+    const size_t lds = count_lds_bytes(w_log2) + (size_t)replicas * facet.n_values * 4;
+    const void* fn = route == COUNT_FAST_ZB ? reinterpret_cast<const void*>(&k_facet_counts<true>) : reinterpret_cast<const void*>(&k_facet_counts<false>);
+    if (lds >= 60 * 1024) PS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  // (with the static words: past 64 KiB)
+    if (route == COUNT_FAST_ZB) hipLaunchKernelGGL(k_facet_counts<true>, dim3((uint32_t)items.size()), dim3(COUNT_NT), lds, st, cp, fp);
+    else hipLaunchKernelGGL(k_facet_counts<false>, dim3((uint32_t)items.size()), dim3(COUNT_NT), lds, st, cp, fp);
     PS_HIP(hipGetLastError());
   }
   publish_tail(m, st);
@@ -3888,6 +4013,42 @@ void Engine::run_count(const ps_scorer_desc& sc, const double* boosts, const Pla
   stats.n_plan_entries = plan.entries.size();
   stats.postings_visited = plan.postings;
   stats.algorithmic_bytes = plan.postings * 4 + (uint64_t)B * 8;  // the doc-id plane alone + the totals
+  stats.layout_bytes = stats.algorithmic_bytes;
+  stats.total_ms = now_ms() - t0;
+}
+
+void Engine::run_facet_counts(const ps_scorer_desc& sc, const double* boosts, const Plan& plan, const ps_facet& facet, void* d_counts,
+                              uint64_t* h_counts, void* stream, ps_batch_stats& stats) {
+  EngineImpl& m = *impl_;
+  const Snapshot& s = *m.snap;
+  const size_t B = plan.qbeg.size() - 1, n = B * facet.n_values;
+  validate(s, sc, plan);
+  check_filter(m, sc);
+  if (facet.state != m.state)
+    throw std::invalid_argument("the facet was made from another snapshot, or before ps_snapshot_update changed this one: create it again");
+  std::lock_guard<std::mutex> lock(m.mu);
+  PS_HIP(hipSetDevice(m.device));
+  const double t0 = now_ms();
+  hipStream_t st = (!h_counts && stream) ? (hipStream_t)stream : m.stream;
+  if (h_counts) {
+    m.d_count_totals.ensure(n + 1);
+    m.result.ensure(n * 8 + 64);
+  }
+  unsigned long long* dc = h_counts ? m.d_count_totals.p : static_cast<unsigned long long*>(d_counts);
+  try {
+    enqueue_facet_counts(m, sc, boosts, plan, facet, dc, st);
+    if (h_counts && n) PS_HIP(hipMemcpyAsync(m.result.p, dc, n * 8, hipMemcpyDeviceToHost, st));
+    if (h_counts || !stream) sync_stream(st);
+  } catch (...) {
+    (void)hipStreamSynchronize(st);  // nothing may still be reading the staging slot
+    throw;
+  }
+  if (h_counts && n) memcpy(h_counts, m.result.p, n * 8);
+  memset(&stats, 0, sizeof(stats));
+  stats.n_queries = B;
+  stats.n_plan_entries = plan.entries.size();
+  stats.postings_visited = plan.postings;
+  stats.algorithmic_bytes = plan.postings * 4 + (uint64_t)n * 8;  // the doc-id plane alone + the counts
   stats.layout_bytes = stats.algorithmic_bytes;
   stats.total_ms = now_ms() - t0;
 }

@@ -19,6 +19,15 @@ struct ps_filter {
   uint64_t len = 0;             // their number
 };
 
+// The handle behind the C ABI's ps_facet: one value id per document, resolved on one engine's device (Engine::facet_new).
+struct ps_facet {
+  uint64_t state = 0;          // the engine state it was made from, as ps_filter's
+  int device = -1;
+  uint16_t* d_col = nullptr;   // value + 1 per doc id (0 = none), padded like the alive bitmap
+  uint32_t n_values = 0;
+  uint64_t len = 0;            // alive documents that carry a value
+};
+
 namespace ps {
 
 struct EngineImpl;
@@ -129,6 +138,17 @@ class Engine {
   // is always planned on the host; it throws std::invalid_argument unless the filter was made by THIS engine in its current state.
   ps_filter* filter_new(const uint64_t* keys, size_t n_keys);
 
+  // Resolves (key, value) pairs (any order, unknown keys ignored, the largest value of a repeated key) into a facet's
+  // value column on the device: k_facet_build (ps_kernels_facet.hpp).  Synchronous; the length comes down once.  The
+  // caller has checked values[i] < n_values <= PS_MAX_FACET_VALUES.
+  ps_facet* facet_new(const uint64_t* keys, const uint32_t* values, size_t n, uint32_t n_values);
+  // Facet counts - counts[q * n_values + v]: the documents of query q's full result list whose value is v - of a
+  // host-planned batch: Kh k_facet_counts where run_count takes k_count_matches, stage 1 of the deep path and
+  // Kr k_facet_runs where it takes the slow route.  h_counts / d_counts / stream as run_count's totals, u64[B * n_values].
+  // Throws std::invalid_argument unless the facet was made by THIS engine in its current state.
+  void run_facet_counts(const ps_scorer_desc& sc, const double* boosts, const Plan& plan, const ps_facet& facet, void* d_counts,
+                        uint64_t* h_counts, void* stream, ps_batch_stats& stats);
+
   // SURVEY 8f N2 - device-side planner (BM25 and zero_to_one, built-in tokenizer): tokenise, term lookup in the frozen
   // trie, prefix expansion and before_each run on the GPU.  plan_device copies the plan back (tests);
   // run_device_planned scores the batch without the plan ever existing on the host.
@@ -161,6 +181,7 @@ class Engine {
 };
 
 void filter_free(ps_filter* f);  // (device memory: freed on the filter's device, whether or not its engine still exists)
+void facet_free(ps_facet* f);    // (the same)
 int device_count();
 // Tuning knobs by name (the PS_* names of DESIGN.md section 11); read when a snapshot's engine is created.
 void set_option(const char* name, uint32_t value);

@@ -7,6 +7,7 @@
 //   ps_kernels_count.hpp   Kc k_count_matches, k_count_copy                                           (exact total match counts)
 //   ps_kernels_conj.hpp    Kj k_conj                                                                  (match-all queries: intersect-and-score stage 1)
 //   ps_kernels_filter.hpp  k_filter_build (mark, count, scan, scatter), Kf k_filter_score              (document filters: filter-driven stage 1)
+//   ps_kernels_facet.hpp   k_facet_build (assign, narrow), Kh k_facet_counts, Kr k_facet_runs          (facet counts: per-value match histograms)
 // (the device-side preparation of a K1d batch: ps_prep_kernels.hpp; zero_to_one's pruning kernel: ps_z21_daat.hpp).  Included by
 // ps_engine.hip only (one translation unit); see that file's header comment for the kernel overview and DESIGN.md section 3.
 #pragma once
@@ -18,3 +19,4 @@
 #include "ps_kernels_count.hpp"
 #include "ps_kernels_conj.hpp"
 #include "ps_kernels_filter.hpp"
+#include "ps_kernels_facet.hpp"

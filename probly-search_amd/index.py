@@ -228,6 +228,43 @@ class Filter:
             pass
 
 
+class Facet:
+    """One value id per document, resolved on a Snapshot's device (ps_facet).  len(): the alive documents that carry a
+    value; n_values: the number of bins a count call returns per query."""
+
+    def __init__(self, snapshot, keys, values, n_values=None):
+        import numpy as np
+        self._L = _lib.load()
+        self._snap = snapshot  # a facet is of use with its snapshot only: keep it alive
+        k = np.ascontiguousarray(np.asarray(list(keys) if not hasattr(keys, "dtype") else keys, dtype=np.uint64))
+        v = np.ascontiguousarray(np.asarray(list(values) if not hasattr(values, "dtype") else values, dtype=np.uint32))
+        if k.shape != v.shape or k.ndim != 1:
+            raise ValueError("keys and values must be one-dimensional and of the same length")
+        if n_values is None:
+            n_values = int(v.max()) + 1 if v.size else 1
+        self._h = C.c_void_p()
+        _lib.check(self._L.ps_snapshot_facet_new(snapshot._h, k.ctypes.data if k.size else None, v.ctypes.data if v.size else None,
+                                                 k.size, n_values, C.byref(self._h)))
+
+    @property
+    def n_values(self):
+        return int(self._L.ps_facet_values(self._h))
+
+    def __len__(self):
+        return int(self._L.ps_facet_len(self._h))
+
+    def close(self):
+        if self._h:
+            self._L.ps_facet_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Snapshot:
     """Immutable flattened CSR view of an Index, resident in HBM (ps_snapshot)."""
 
@@ -411,6 +448,43 @@ class Snapshot:
             _lib.check(self._L.ps_snapshot_count_batch_device_flat(
                 self._h, C.byref(desc), text.ctypes.data, offsets.ctypes.data, len(offsets) - 1, b, nb, None, None,
                 d_totals, stream if stream else None))
+        except PsError as e:
+            _raise(e)
+
+    def facet(self, keys, values, n_values=None):
+        """ps_snapshot_facet_new: document keys[i] carries the value id values[i] < n_values (default: max + 1) -> Facet,
+        for the facet counts below.  Keys in any order; unknown keys are ignored, an unlisted document has no value, a key
+        listed more than once takes the largest of its values.  It serves this snapshot until update() changes it."""
+        return Facet(self, keys, values, n_values)
+
+    def facet_counts_batch(self, queries, score_calculator, fields_boost, facet, tokenizer=None, match="any", filter=None):
+        """Facet counts -> numpy uint64[B, facet.n_values]: counts[i, v] is the number of documents of
+        query(queries[i], ..., top_k=0) whose facet value is v, for every value of every query in one launch
+        (k_facet_counts: count_batch's bitset of matches, histogrammed over the facet's value column in LDS).  match and
+        filter: as count_batch."""
+        import numpy as np
+        qb, arr = self._pack_queries(queries)
+        desc = _scorer_desc(score_calculator, match, filter=filter)
+        b, nb = _boosts(fields_boost)
+        tok = _Tok(tokenizer)
+        counts = np.empty((len(qb), facet.n_values if facet is not None else 0), np.uint64)
+        try:
+            _lib.check(self._L.ps_snapshot_facet_counts_batch(self._h, C.byref(desc), arr, len(qb), b, nb, tok.ptr, None,
+                                                              facet._h if facet is not None else None, counts.ctypes.data))
+        except PsError as e:
+            _raise(e)
+        return counts
+
+    def facet_counts_batch_device_flat(self, text, offsets, score_calculator, fields_boost, facet, d_counts, stream=None, match="any",
+                                       filter=None):
+        """facet_counts_batch into d_counts, a device pointer (int) to u64[B * facet.n_values] on this snapshot's device;
+        text / offsets / stream as count_batch_device_flat (ps_snapshot_facet_counts_batch_device_flat)."""
+        desc = _scorer_desc(score_calculator, match, filter=filter)
+        b, nb = _boosts(fields_boost)
+        try:
+            _lib.check(self._L.ps_snapshot_facet_counts_batch_device_flat(
+                self._h, C.byref(desc), text.ctypes.data, offsets.ctypes.data, len(offsets) - 1, b, nb, None, None,
+                facet._h if facet is not None else None, d_counts, stream if stream else None))
         except PsError as e:
             _raise(e)
 
